@@ -12,6 +12,15 @@ N = 1: RMAT scale 24 on one MI355X (configs[2]).
 N > 1: weak scaling, RMAT scale 24 + log2(N) (N = 8 -> scale 27, configs[3]), 1-D vertex
        partitioned, one process per GPU, RCCL exchanges (titan_amd/distributed.py).
 Launch: python bench.py [--steps K --warmup W]; N > 1 via torch.distributed.run.
+
+A plain run does what the headline figure needs and no more: it builds and loads the graphs,
+counts the reached edges once (untimed), warms up, times the K steps and prints the result
+line.  --full adds every side measurement to that line: the sweep's self-check against
+single-source runs, the single-source GTEPS over all roots, the delta-stepping SSSP leg, the
+edgestore-rows leg and the CPU oracle baseline (each with its own switch, see --help).
+--dump-outputs DIR writes what the last timed step left as results (one GPU): the BFS levels
+of every root and the PageRank vector on a fixed, seeded sample of the vertices, as float64
+.npy files, so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -60,7 +69,13 @@ def parse():
     p.add_argument("--edge-factor", type=int, default=16)
     p.add_argument("--roots", type=int, default=64)
     p.add_argument("--pr-iters", type=int, default=20)
-    p.add_argument("--cpu-baseline", type=int, default=1, help="0 disables the oracle timing")
+    p.add_argument("--full", action="store_true",
+                   help="also run the side measurements (self-check, single-source BFS, SSSP leg, rows leg, CPU "
+                        "baseline); without it only the timed steps run and those keys of the result line are null")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's results (sampled BFS levels and PageRank) "
+                        "as DIR/<name>.npy (one-GPU path)")
+    p.add_argument("--cpu-baseline", type=int, default=1, help="with --full: 0 disables the oracle timing")
     p.add_argument("--cpu-threads", type=int, default=0, help="oracle threads (0 = every CPU this process may use)")
     p.add_argument("--rows-scale", type=int, default=20,
                    help="configs[1]: single-source BFS over byte-exact edgestore rows of this RMAT scale (0 = off)")
@@ -77,7 +92,10 @@ def parse():
                    help="partitioned PageRank: ghost exchange (only the contributions a rank reads) or all-gather")
     p.add_argument("--balanced", type=int, default=1,
                    help="partitioned path: edge-balanced ranges (entries + vertices, SlotPartition); 0 = equal ranges")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 PMC_FILE = os.path.join(ROOT, "profiles", "pmc_traffic.json")
@@ -121,6 +139,7 @@ def result_line(args, world, scale, n, m, roots, elapsed, teps, hmean, pr_s_iter
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": round(elapsed / args.steps * 1e3, 3),
         "higher_is_better": True,
         "scaling": "weak",
@@ -171,23 +190,25 @@ def run_single(args):
     # per-root reached counts (untimed): m_R, n_R for GTEPS and algorithmic bytes
     bfs_eng.bfs_multi(roots, n, L.SCOPE_BOTH_E, seed_is_dense=True, stats=True, fetch=False)
     nR, mR = bfs_eng.multi_stats(len(roots))
-    # self-check (untimed): two of the sweep's sources against their single-source runs
-    import ctypes as C
-    ms = np.empty(n, np.int64)
-    checked = 0
-    for i in (0, len(roots) - 1):
-        bfs_eng.lib.tgo_copy_multi_distances(bfs_eng.ctx, i, L.ptr(ms, C.c_int64))
-        checked += int(np.array_equal(ms, bfs_eng.bfs(int(roots[i]), n, L.SCOPE_BOTH_E, seed_is_dense=True)))
-    # single-source side measurement (untimed, Graph500 style: every one of the 64 roots)
-    ss_t, depth0 = [], 1
-    for i, r in enumerate(roots):
-        bfs_eng.bfs(int(r), n, L.SCOPE_BOTH_E, seed_is_dense=True, fetch=False)
-        t = time.perf_counter()
-        bfs_eng.bfs(int(r), n, L.SCOPE_BOTH_E, seed_is_dense=True, fetch=False)
-        ss_t.append(time.perf_counter() - t)
-        if i == 0:
-            depth0 = bfs_eng.stats()["levels"]
-    ss_hmean = len(ss_t) / float(np.sum(np.array(ss_t) / (mR[:len(ss_t)] / 2.0)))
+    checked, ss_hmean, depth0 = None, None, 1
+    if args.full:
+        # self-check (untimed): two of the sweep's sources against their single-source runs
+        import ctypes as C
+        ms = np.empty(n, np.int64)
+        checked = 0
+        for i in (0, len(roots) - 1):
+            bfs_eng.lib.tgo_copy_multi_distances(bfs_eng.ctx, i, L.ptr(ms, C.c_int64))
+            checked += int(np.array_equal(ms, bfs_eng.bfs(int(roots[i]), n, L.SCOPE_BOTH_E, seed_is_dense=True)))
+        # single-source side measurement (untimed, Graph500 style: every one of the 64 roots)
+        ss_t = []
+        for i, r in enumerate(roots):
+            bfs_eng.bfs(int(r), n, L.SCOPE_BOTH_E, seed_is_dense=True, fetch=False)
+            t = time.perf_counter()
+            bfs_eng.bfs(int(r), n, L.SCOPE_BOTH_E, seed_is_dense=True, fetch=False)
+            ss_t.append(time.perf_counter() - t)
+            if i == 0:
+                depth0 = bfs_eng.stats()["levels"]
+        ss_hmean = len(ss_t) / float(np.sum(np.array(ss_t) / (mR[:len(ss_t)] / 2.0)))
 
     def step():
         t = time.perf_counter()
@@ -205,6 +226,8 @@ def run_single(args):
     res = [step() for _ in range(args.steps)]
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - T0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, n, len(roots), bfs_eng, pr_eng)
     bts = np.array([r[0] for r in res])
     bks = np.array([r[1] for r in res])
     pts = np.array([r[2] for r in res])
@@ -231,21 +254,58 @@ def run_single(args):
                        "4*m + 8*(n+1) + 24*n per update", "pagerank_update", pr_bytes)
     bfs_share = float(bts.sum()) / (float(bts.sum()) + float(pts.sum()))
     del pr_eng, bfs_eng
-    sssp = sssp_leg(args, n, src, dst, roots, cores) if args.sssp_roots > 0 else None
-    rows_leg = config2_rows_leg(args, cores) if args.rows_scale > 0 else None
+    sssp = sssp_leg(args, n, src, dst, roots, cores) if args.full and args.sssp_roots > 0 else None
+    rows_leg = config2_rows_leg(args, cores) if args.full and args.rows_scale > 0 else None
     cpu = None
-    if args.cpu_baseline:
+    if args.full and args.cpu_baseline:
         # levels counts the final empty level; the eccentricity is one less
         cpu = cpu_baseline(args, n, src, dst, roots, mR, max(int(depth[0]) - 1, 1),
                            args.cpu_threads or cores, pr_s_iter_gpu=float(pks.mean()) / upd)
     line = result_line(args, 1, scale, n, m, roots, elapsed, teps, hmean, float(pts.mean()) / upd, e_in,
                        roof_bfs, roof_pr, bfs_share, cpu, "single")
     line["load"] = load
-    line["validation"] = {"msbfs_vs_single_source": f"{checked}/2 sources bit-exact (untimed self-check); "
-                                                    "full-size oracle parity: tests/test_gpu_fullsize.py"}
+    line["validation"] = None if checked is None else {
+        "msbfs_vs_single_source": f"{checked}/2 sources bit-exact (untimed self-check); "
+                                  "full-size oracle parity: tests/test_gpu_fullsize.py"}
     line["sssp"] = sssp
     line["config2_rows"] = rows_leg
     print(json.dumps(line), flush=True)
+
+
+DUMP_SAMPLE = 1 << 16      # vertices dumped: (roots + 2) * 8 B each, 33 MiB at 64 roots
+DUMP_SEED = 0x54495441
+
+
+def dump_outputs(out_dir, n, nroots, bfs_eng, pr_eng):
+    """--dump-outputs: the results the last timed step left on the device (the steps run with
+    fetch=False), copied out the way the fetching calls copy them and written as float64 .npy:
+      sample_vertices (k)        : the dumped vertices (dense ids, ascending): all of them up to
+                                   DUMP_SAMPLE, else a seeded draw without replacement
+      bfs_levels      (roots, k) : tgo_bfs_multi's distances (seed-major; unreached = -2^63)
+      pagerank        (k)        : tgo_pagerank's ranks"""
+    import ctypes as C
+    from titan_amd import _lib as L
+    from titan_amd.engine import TitanException
+
+    def check(eng, rc):
+        if rc:
+            raise TitanException(rc, (eng.lib.tgo_last_error(eng.ctx) or b"").decode())
+    k = min(n, DUMP_SAMPLE)
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+    buf = np.empty(n, np.int64)
+    levels = np.empty((nroots, k), np.float64)
+    for i in range(nroots):
+        check(bfs_eng, bfs_eng.lib.tgo_copy_multi_distances(bfs_eng.ctx, i, L.ptr(buf, C.c_int64)))
+        levels[i] = buf[idx]
+    # tgo_pagerank keeps its ranks in the ctx's 8-byte distance array (the bits of the
+    # doubles) and fetches them with the same un-permuting copy as tgo_copy_distances
+    check(pr_eng, pr_eng.lib.tgo_copy_distances(pr_eng.ctx, L.ptr(buf, C.c_int64)))
+    ranks = buf.view(np.float64)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "sample_vertices.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "bfs_levels.npy"), levels)
+    np.save(os.path.join(out_dir, "pagerank.npy"), np.ascontiguousarray(ranks))
+    log(f"outputs of the last timed step ({k} of {n} vertices, {nroots} roots) written to {out_dir}")
 
 
 def config2_rows_leg(args, cores):
@@ -359,7 +419,7 @@ def run_partitioned(args, world, rank, local_rank):
         cap = int(2.3 * m * (hi - lo) / n) + (1 << 22)
         src = np.empty(cap, np.int32)
         dst = np.empty(cap, np.int32)
-        wgt = np.empty(cap, np.int32) if args.sssp_roots > 0 else None
+        wgt = np.empty(cap, np.int32) if args.full and args.sssp_roots > 0 else None
         cnt = C.c_int64()
         rc = lib.tgo_rmat_partition_device(scale, args.edge_factor, 0x54495441, lo, hi, L.ptr(src, C.c_int32),
                                            L.ptr(dst, C.c_int32), L.ptr(wgt, C.c_int32), cap, C.byref(cnt), local_rank)
@@ -424,13 +484,14 @@ def run_partitioned(args, world, rank, local_rank):
         if xchg is not None:
             return distributed_bfs_native(bfs_be, r, ns, xchg, fetch=False, stats=False)
         return distributed_bfs(bfs_be, r, ns, fetch=False, stats=False)
-    single(roots_s[0])
-    for r in roots_s:
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        single(r)
-        torch.cuda.synchronize()
-        ss_t.append(time.perf_counter() - t)
+    if args.full:
+        single(roots_s[0])
+        for r in roots_s:
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            single(r)
+            torch.cuda.synchronize()
+            ss_t.append(time.perf_counter() - t)
     pr_mode = PR_EXCHANGE_GHOST if args.pr_exchange == "ghost" else PR_EXCHANGE_ALLGATHER
     pr_moved = [0]
 
@@ -439,7 +500,7 @@ def run_partitioned(args, world, rank, local_rank):
             _, pr_moved[0] = distributed_pagerank_native(pr_be, 0.85, n, args.pr_iters, xchg, mode=pr_mode, fetch=False)
         else:
             distributed_pagerank(pr_be, 0.85, n, args.pr_iters, fetch=False, layout=pr_layout)
-    hmean = len(ss_t) / float(np.sum(np.array(ss_t) / (mR[:len(ss_t)] / 2.0)))
+    hmean = len(ss_t) / float(np.sum(np.array(ss_t) / (mR[:len(ss_t)] / 2.0))) if ss_t else None
 
     def step():
         t = time.perf_counter()
@@ -608,6 +669,8 @@ def cpu_baseline(args, n, src, dst, roots, mR, depth, threads, pr_s_iter_gpu=Non
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs and (world > 1 or args.partitioned):
+        sys.exit("bench.py: --dump-outputs covers the one-GPU path; the partitioned path keeps its results per rank")
     if args.partitioned and "RANK" not in os.environ:     # one rank without a launcher
         import socket
         sk = socket.socket()

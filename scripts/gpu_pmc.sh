@@ -10,7 +10,7 @@ mkdir -p $OUT
 run_pass() {   # $1 = dir name, rest = counters
     local d=$1; shift
     timeout -s KILL 300 rocprofv3 --pmc "$@" --output-format csv -d $OUT/$d -o run -- \
-        python3 bench.py --steps 1 --warmup 0 --cpu-baseline 0 $BENCH_ARGS > $OUT/$d.log 2>&1
+        python3 bench.py --full --steps 1 --warmup 0 --cpu-baseline 0 $BENCH_ARGS > $OUT/$d.log 2>&1
     local rc=$?
     echo "pass $d ($*) exit $rc"
     return $rc
