@@ -373,6 +373,27 @@ int  tgo_pagerank(tgo_ctx* ctx, const tgo_pr_args* args, double* pr_out);
 /* OLAPTest.DegreeCounter(k) (OLAPTest.java:334-416): k-walk counts, Java int wrap. */
 int  tgo_walkcount(tgo_ctx* ctx, int32_t k, int32_t* out);
 
+/* ---- Weakly connected components ------------------------------------------------------
+ * label_out[v] = the fixed point of MIN label propagation over the loaded bothE lists with
+ * Titan ids as labels: the smallest Titan id among v and every vertex whose label reaches v
+ * along the pull lists — with consistent lists (every bothE load from rows or edges) the
+ * smallest Titan id of v's weakly connected component; a vertex cut is labelled by canonical
+ * ids, an isolated vertex by its own.  The fixed point is unique: results are bit-identical
+ * run to run.  args->scope must be TGO_SCOPE_BOTH_E and the loaded scope; args->flags 0.
+ *   TGO_CC_HOOK       lists that are each other's transpose: concurrent hook-and-compress
+ *                     (union-find by atomic compare-and-swap, pointer jumping) over the OUT lists
+ *   TGO_CC_PROPAGATE  other lists (tgo_load_csr with asymmetric rows): MIN pull, round by round
+ * info->rounds (also tgo_stats.iterations) counts DEVICE rounds — hook and pointer-jumping
+ * launches, or pull rounds — NOT the supersteps the label-propagation vertex program would
+ * take (its count grows with the diameter; the hook path's does not).  info->components =
+ * distinct labels.  label_out NULL: the labels stay on the device (tgo_copy_components,
+ * tgo_result_rows kind TGO_RESULT_COMPONENT). */
+typedef enum { TGO_CC_HOOK = 0, TGO_CC_PROPAGATE = 1 } tgo_cc_path;
+typedef struct { int32_t scope; int32_t flags; } tgo_cc_args;
+typedef struct { int64_t components; int32_t rounds; int32_t path; } tgo_cc_info;
+int  tgo_components(tgo_ctx* ctx, const tgo_cc_args* args, int64_t* label_out, tgo_cc_info* info);
+int  tgo_copy_components(tgo_ctx* ctx, int64_t* label_out);
+
 /* ---- Generic vertex programs ----------------------------------------
  * A vertex program the engine does not implement natively runs its execute() on the host
  * over whole per-vertex vectors (titan_amd/computer.py GenericVertexProgram; the Java host
@@ -474,6 +495,8 @@ int  tgo_dense_ids(tgo_ctx* ctx, const int64_t* titan_ids, int64_t count, int64_
  *   PAGERANK  PAGE_RANK and OUTGOING_EDGE_COUNT (Double) on every executed vertex once
  *             iterations >= 1 (PageRankVertexProgram.java:79-88)
  *   DEGREE    OLAPTest.DegreeCounter DEGREE (Integer) on every executed vertex
+ *   COMPONENT tgo_components' label (Long; an Integer key when every Titan id of the graph is
+ *             in int range, else TGO_E_INVALID) on every executed vertex
  * Compute keys are typed property keys of those datatypes, or generic keys (TGO_DT_OBJECT: what
  * getOrCreatePropertyKey makes for a key the program sets without a schema, DefaultSchemaMaker
  * .java:46-48), whose values carry their class (Long 13, Double 20, Integer 12).  Relation ids are
@@ -482,11 +505,11 @@ int  tgo_dense_ids(tgo_ctx* ctx, const int64_t* titan_ids, int64_t count, int64_
  * nrows keys, nrows+1 entry / byte offsets, nbytes bytes and nentries limit|valuePos words
  * (the tgo_rows layout, so the rows can be scanned again). */
 typedef enum { TGO_RESULT_DISTANCE = 0, TGO_RESULT_PAGERANK = 1, TGO_RESULT_DEGREE = 2,
-               TGO_RESULT_VALUES = 3 } tgo_result_kind;
+               TGO_RESULT_VALUES = 3, TGO_RESULT_COMPONENT = 4 } tgo_result_kind;
 typedef struct {
     int32_t kind;                 /* tgo_result_kind                                          */
     int32_t reserved;             /* TGO_RESULT_VALUES: tgo_value_type of the values           */
-    int64_t key_ids[2];           /* [0] DISTANCE / PAGE_RANK / DEGREE key; [1] OUTGOING_EDGE_COUNT */
+    int64_t key_ids[2];           /* [0] DISTANCE / PAGE_RANK / DEGREE / COMPONENT key; [1] OUTGOING_EDGE_COUNT */
     int32_t datatypes[2];         /* tgo_datatype of each key                                  */
     int64_t relation_id_base;
 } tgo_result_args;

@@ -273,6 +273,20 @@ JNIEXPORT jintArray JNICALL JFN(walkCount)(JNIEnv* env, jclass cls, jlong h, jin
     return rc == TGO_OK ? out : NULL;
 }
 
+/* tgo_components over the bothE load: the labels in row order, or NULL on error (the rounds are
+ * tgo_stats.iterations afterwards). */
+static int run_components(tgo_ctx* c, const void* a, int64_t* o) {
+    return tgo_components(c, (const tgo_cc_args*)a, o, NULL);
+}
+
+JNIEXPORT jlongArray JNICALL JFN(components)(JNIEnv* env, jclass cls, jlong h) {
+    (void)cls;
+    tgo_cc_args a;
+    memset(&a, 0, sizeof a);
+    a.scope = TGO_SCOPE_BOTH_E;
+    return distances(env, h, run_components, &a);
+}
+
 /* tgo_result_rows: Object[5] = {long[] rowKeys, long[] rowEntryBegin, long[] rowByteBegin,
  * long[] entryLimitValuePos, byte[] entryBytes}, or NULL on error (status: lastError; a result
  * beyond the int32 index range of a Java array: IllegalStateException). */

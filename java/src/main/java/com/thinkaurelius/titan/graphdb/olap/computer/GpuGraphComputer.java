@@ -43,7 +43,8 @@ import java.util.concurrent.Future;
  *
  * Supported: tmain's PageRankVertexProgram, ShortestDistanceVertexProgram and
  * OLAPTest.DegreeCounter (matched by class name; their parameters are read from
- * storeState(), or the DegreeCounter's length field).
+ * storeState(), or the DegreeCounter's length field), and a ConnectedComponentVertexProgram
+ * (weakly connected components over bothE, tgo_components).
  *
  * Write-back (FulgoraGraphComputer.java:248-305): with Persist.VERTEX_PROPERTIES the compute
  * keys are encoded on the device (tgo_result_rows: single-cardinality property entries, one
@@ -534,6 +535,8 @@ public class GpuGraphComputer implements TitanGraphComputer {
                             conf.getString("titan.shortestDistanceVertexProgram.weightProperty", "distance"));
                 case "com.thinkaurelius.titan.olap.OLAPTest$DegreeCounter":
                     return new DegreeCount(lengthOf(p));
+                case "com.thinkaurelius.titan.olap.ConnectedComponentVertexProgram":
+                    return new ConnectedComponent();
                 default:
                     throw new TitanException("vertex program " + p.getClass().getName() + " is not supported on the GPU path");
             }
@@ -652,6 +655,31 @@ public class GpuGraphComputer implements TitanGraphComputer {
         void emit(long[] ids, Map<String, Object> values, FulgoraMapEmitter emitter) {
             int[] d = (int[]) values.get("degree");
             for (int i = 0; i < ids.length; i++) emitter.emit(ids[i], d[i]);
+        }
+    }
+
+    /**
+     * Weakly connected components over bothE (tgo_components): COMPONENT = the smallest vertex id
+     * of the component, the fixed point of MIN label propagation.  The iteration reported is the
+     * number of device rounds, known after run(), not the propagation's superstep count.
+     */
+    static final class ConnectedComponent extends DeviceProgram {
+        static final String COMPONENT = "titan.connectedComponent.component";
+        private int rounds;
+        int scope() { return TgoNative.SCOPE_BOTH_E; }
+        int iterations() { return rounds; }
+        int resultKind() { return TgoNative.RESULT_COMPONENT; }
+        String[] computeKeys() { return new String[]{COMPONENT}; }
+        int[] computeKeyTypes() { return new int[]{TgoNative.DT_LONG}; }
+        Map<String, Object> run(long ctx) {
+            Map<String, Object> v = new HashMap<>();
+            v.put(COMPONENT, TgoNative.checked(ctx, TgoNative.components(ctx)));
+            rounds = (int) TgoNative.stats(ctx)[3];
+            return v;
+        }
+        void emit(long[] ids, Map<String, Object> values, FulgoraMapEmitter emitter) {
+            long[] c = (long[]) values.get(COMPONENT);
+            for (int i = 0; i < ids.length; i++) emitter.emit(ids[i], c[i]);
         }
     }
 }

@@ -75,11 +75,18 @@ public final class TgoNative {
 
     public static native int[] walkCount(long ctx, int length);
 
+    /**
+     * tgo_components over a bothE load: every vertex's component label (the smallest Titan id of
+     * its weakly connected component) in row order; null on failure.  stats()[3] then holds the
+     * device rounds, which are not the supersteps of a label-propagation program.
+     */
+    public static native long[] components(long ctx);
+
     /** tgo_stats_get: {ghostVertices, truncatedResults, skippedRows, iterations, loadMs, lastKernelMs}. */
     public static native double[] stats(long ctx);
 
     /** tgo_result_kind */
-    public static final int RESULT_DISTANCE = 0, RESULT_PAGERANK = 1, RESULT_DEGREE = 2;
+    public static final int RESULT_DISTANCE = 0, RESULT_PAGERANK = 1, RESULT_DEGREE = 2, RESULT_COMPONENT = 4;
     /**
      * tgo_result_rows: the edgestore entries (single-cardinality property entries) of the last
      * program's compute keys, as {long[] rowKeys, long[] rowEntryBegin, long[] rowByteBegin,

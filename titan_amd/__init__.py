@@ -6,6 +6,7 @@ TitanGraphComputer API plus a thin ctypes binding; it has no CPU fallback.
 """
 from .engine import Engine, Rows, Schema, TitanException, rmat_edges, pick_roots, synth_rows  # noqa: F401
 from .computer import (  # noqa: F401
+    ClusterCountMapReduce, ClusterPopulationMapReduce, ConnectedComponentVertexProgram,
     DegreeCounter, DegreeMapper, ExecutionException, GpuGraph, GpuGraphComputer, KeyValue,
     PageRankMapReduce, PageRankVertexProgram, ShortestDistanceMapReduce,
     ShortestDistanceVertexProgram, TitanGraphComputer,
@@ -22,4 +23,5 @@ __all__ = [
     "PageRankVertexProgram", "ShortestDistanceMapReduce", "ShortestDistanceVertexProgram",
     "TitanGraphComputer", "ComputeKeyMapReduce", "FulgoraMemory", "GenericVertexProgram", "MessageScope",
     "Messenger", "Vertices", "EdgeExpr", "TraversalVertexProgram",
+    "ConnectedComponentVertexProgram", "ClusterPopulationMapReduce", "ClusterCountMapReduce",
 ]

@@ -31,6 +31,8 @@ DT_OBJECT = 11      # generic key (DefaultSchemaMaker: dataType(Object.class)); 
 DT_DATE, DT_CHARACTER, DT_STRING = 8, 9, 10
 ORDER_ASC, ORDER_DESC = 0, 1
 RESULT_DISTANCE, RESULT_PAGERANK, RESULT_DEGREE, RESULT_VALUES = 0, 1, 2, 3
+RESULT_COMPONENT = 4
+CC_HOOK, CC_PROPAGATE = 0, 1     # tgo_cc_path
 SSSP_HOP_BOUNDED, SSSP_DELTA = 0, 1
 FLAG_STATS = 1
 TUNE_MS_SPLIT, TUNE_MS_GHOST, TUNE_DS_BINS, TUNE_DS_PILE_CAP, TUNE_DS_DONE, TUNE_MS_COLD, TUNE_DS_PULL = 1, 2, 3, 4, 5, 6, 7   # tgo_set_tuning keys
@@ -126,6 +128,14 @@ class PrArgs(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class CcArgs(C.Structure):
+    _fields_ = [("scope", C.c_int32), ("flags", C.c_int32)]
+
+
+class CcInfo(C.Structure):
+    _fields_ = [("components", C.c_int64), ("rounds", C.c_int32), ("path", C.c_int32)]
+
+
 class GatherArgs(C.Structure):
     _fields_ = [("scope", C.c_int32), ("value_type", C.c_int32), ("combiner", C.c_int32), ("edge_fn", C.c_int32)]
 
@@ -154,6 +164,7 @@ EXPORTS = [
     "tgo_trace_enable", "tgo_trace_flush", "tgo_trace_clear", "tgo_trace_range_push", "tgo_trace_range_pop",
     "tgo_gather", "tgo_combine_global", "tgo_dense_ids", "tgo_decode_edge_entry", "tgo_result_rows",
     "tgo_gather_lists", "tgo_result_rows_values", "tgo_set_edge_program",
+    "tgo_components", "tgo_copy_components",
     "tgo_rmat_edges", "tgo_rmat_edges_device", "tgo_rmat_partition_device", "tgo_pick_roots", "tgo_synth_rows",
     # titan_gpu_olap_part.h (1-D vertex-partitioned multi-GPU)
     "tgo_load_partition", "tgo_part_layout", "tgo_load_partition_layout", "tgo_part_bfs_begin", "tgo_part_bfs_td", "tgo_part_bfs_claim", "tgo_part_bfs_bu",
@@ -210,6 +221,8 @@ def load() -> C.CDLL:
         "tgo_bfs": (C.c_int, [vp, P(BfsArgs), _i64p]),
         "tgo_sssp": (C.c_int, [vp, P(SsspArgs), _i64p]),
         "tgo_copy_distances": (C.c_int, [vp, _i64p]),
+        "tgo_components": (C.c_int, [vp, P(CcArgs), _i64p, P(CcInfo)]),
+        "tgo_copy_components": (C.c_int, [vp, _i64p]),
         "tgo_pagerank": (C.c_int, [vp, P(PrArgs), C.POINTER(C.c_double)]),
         "tgo_walkcount": (C.c_int, [vp, C.c_int32, _i32p]),
         "tgo_stats_get": (C.c_int, [vp, P(Stats)]),

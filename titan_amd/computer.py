@@ -358,6 +358,25 @@ class DegreeCounter(VertexProgram):
         self.length = length
 
 
+class ConnectedComponentVertexProgram(VertexProgram):
+    """Weakly connected components over bothE: COMPONENT = the smallest Titan id of the vertex's
+    component — the fixed point of MIN label propagation, which the device reaches by
+    hook-and-compress (tgo_components) instead of one superstep per hop.  Deviation, as with
+    deltaStepping(): memory.getIteration() reports the device rounds, not the supersteps the
+    propagation would take."""
+    COMPONENT = "titan.connectedComponent.component"
+    compute_keys = (COMPONENT,)
+    scope_name = "bothE"
+
+    class Builder:
+        def create(self, graph=None):
+            return ConnectedComponentVertexProgram()
+
+    @staticmethod
+    def build():
+        return ConnectedComponentVertexProgram.Builder()
+
+
 # ----------------------------------------------------------------------------- map-reduces
 class MapReduce:
     memory_key = ""
@@ -418,6 +437,53 @@ class ShortestDistanceMapReduce(MapReduce):
         if d is None:
             return []
         return [KeyValue(int(i), int(v)) for i, v in zip(ids, d) if v != L.DIST_ABSENT]
+
+
+class _MemoryKeyBuilder:
+    def __init__(self, cls):
+        self._cls, self._k = cls, cls.DEFAULT_MEMORY_KEY
+
+    def memoryKey(self, k):  # noqa: N802
+        self._k = k
+        return self
+
+    def create(self):
+        return self._cls(self._k)
+
+
+class ClusterPopulationMapReduce(MapReduce):
+    """Component label -> number of vertices carrying it."""
+    DEFAULT_MEMORY_KEY = "clusterPopulation"
+
+    def __init__(self, key=DEFAULT_MEMORY_KEY):
+        self.memory_key = key
+
+    @staticmethod
+    def build():
+        return _MemoryKeyBuilder(ClusterPopulationMapReduce)
+
+    def emit(self, ids, props):
+        lab = props.get(ConnectedComponentVertexProgram.COMPONENT)
+        if lab is None:
+            return {}
+        u, c = np.unique(np.asarray(lab, dtype=np.int64), return_counts=True)
+        return {int(k): int(v) for k, v in zip(u, c)}
+
+
+class ClusterCountMapReduce(MapReduce):
+    """Number of distinct component labels."""
+    DEFAULT_MEMORY_KEY = "clusterCount"
+
+    def __init__(self, key=DEFAULT_MEMORY_KEY):
+        self.memory_key = key
+
+    @staticmethod
+    def build():
+        return _MemoryKeyBuilder(ClusterCountMapReduce)
+
+    def emit(self, ids, props):
+        lab = props.get(ConnectedComponentVertexProgram.COMPONENT)
+        return 0 if lab is None else int(len(np.unique(np.asarray(lab, dtype=np.int64))))
 
 
 class DegreeMapper(MapReduce):
@@ -541,7 +607,8 @@ class GpuGraphComputer(TitanGraphComputer):
     _RESULT_KEYS = {ShortestDistanceVertexProgram: (L.RESULT_DISTANCE, (ShortestDistanceVertexProgram.DISTANCE,)),
                     PageRankVertexProgram: (L.RESULT_PAGERANK, (PageRankVertexProgram.PAGE_RANK,
                                                                 PageRankVertexProgram.OUTGOING_EDGE_COUNT)),
-                    DegreeCounter: (L.RESULT_DEGREE, (DegreeCounter.DEGREE,))}
+                    DegreeCounter: (L.RESULT_DEGREE, (DegreeCounter.DEGREE,)),
+                    ConnectedComponentVertexProgram: (L.RESULT_COMPONENT, (ConnectedComponentVertexProgram.COMPONENT,))}
 
     def _result_mode(self):
         """resultMode if set, else the program's preferred (ResultGraph, Persist) as Fulgora
@@ -629,6 +696,11 @@ class GpuGraphComputer(TitanGraphComputer):
             eng = self.graph.engine_for(L.SCOPE_IN_E)
             props[DegreeCounter.DEGREE] = eng.walkcount(p.length)
             iteration = p.length
+            ids = eng.vertex_ids()
+        elif isinstance(p, ConnectedComponentVertexProgram):
+            eng = self.graph.engine_for(L.SCOPE_BOTH_E)
+            props[ConnectedComponentVertexProgram.COMPONENT], info = eng.components()
+            iteration = info["rounds"]
             ids = eng.vertex_ids()
         else:
             raise TitanException(L.TGO_E_UNSUPPORTED, f"vertex program {type(p).__name__} is not supported on the GPU path")

@@ -1973,6 +1973,134 @@ int tgo_copy_distances(tgo_ctx* ctx, int64_t* dist_out) {
     return TGO_OK;
 }
 
+// ------------------------------------------------------------------ connected components
+// Weakly connected components (cc.hip).  Device arrays: parent = sc.level (int32), the per-root
+// minimum = sc.vec[0] (as int64), labels in internal order = sc.dist, row-order staging = sc.msg.
+// "changed" / "roots" words: Counters::qlen / red[0], read through the published mirror.
+static int cc_word(tgo_ctx* ctx, bool roots, unsigned long long& out) {
+    if (int rc = read_counters(ctx)) return rc;
+    out = roots ? ctx->sc.hcnt->red[0] : ctx->sc.hcnt->qlen;
+    return TGO_OK;
+}
+
+// Flatten the parent trees: pointer-jumping launches until one finds every vertex under a root.
+static int cc_compress(tgo_ctx* ctx, int32_t& rounds) {
+    Scratch& s = ctx->sc;
+    for (;;) {
+        HIP_TRY(k_level_prep(s.cnt, nullptr, 0, nullptr, ctx->stream));
+        {
+            DevSpan span(ctx->stream, "components.jump", {"round", rounds});
+            HIP_TRY(k_cc_jump(s.level, ctx->g.n, &s.cnt->qlen, ctx->stream));
+        }
+        ++rounds;
+        unsigned long long changed = 0;
+        if (int rc = cc_word(ctx, false, changed)) return rc;
+        if (!changed) return TGO_OK;
+    }
+}
+
+int tgo_components(tgo_ctx* ctx, const tgo_cc_args* a, int64_t* label_out, tgo_cc_info* info) {
+    if (!ctx) return TGO_E_INVALID;
+    ctx->res_kind = -1;
+    if (!a) return fail(ctx, TGO_E_INVALID, "null args");
+    int rc = check_program(ctx, a->scope);
+    if (rc) return rc;
+    if (a->scope != TGO_SCOPE_BOTH_E)
+        return fail(ctx, TGO_E_INVALID, "connected components run over bothE; load the graph with TGO_SCOPE_BOTH_E");
+    if (a->flags != 0) return fail(ctx, TGO_E_INVALID, "tgo_cc_args.flags must be 0");
+    if (ctx->g.partitioned) return fail(ctx, TGO_E_UNSUPPORTED, "connected components run on a one-GPU load");
+    (void)hipSetDevice(ctx->opts.device);
+    DevGraph& g = ctx->g;
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    const int64_t n = g.n;
+    int64_t* const label = s.dist;
+    if (!g.cc_tid) {                // Titan id of every internal index: once per graph
+        HIP_TRY(dev_alloc(ctx, g.cc_tid, n));
+        ctx->st.device_bytes = ctx->dev_bytes;
+        HIP_TRY(hipMemcpyAsync(s.msg, ctx->titan_id.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(k_cc_scatter_ids(s.msg, g.perm, g.cc_tid, n, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    HIP_TRY(hipEventRecord(ctx->ev0, st));
+    int32_t rounds = 0;
+    const int path = g.has_transpose ? TGO_CC_PROPAGATE : TGO_CC_HOOK;
+    unsigned long long components = 0;
+    if (path == TGO_CC_HOOK) {
+        // every edge sits once in the OUT lists; the first entries are hooked and flattened
+        // first so that the bulk of the entries meets short trees
+        int32_t* const parent = s.level;
+        int64_t* const minid = reinterpret_cast<int64_t*>(s.vec[0]);
+        HIP_TRY(k_cc_init(parent, n, st));
+        {
+            DevSpan span(st, "components.hook_sample");
+            HIP_TRY(k_cc_hook(g.out, n, 0, 2, parent, st));
+            HIP_TRY(k_cc_hook(g.in, n, 0, 1, parent, st));
+        }
+        rounds += 2;
+        if ((rc = cc_compress(ctx, rounds))) return rc;
+        {
+            DevSpan span(st, "components.hook_rest");
+            HIP_TRY(k_cc_hook(g.out, n, 2, -1, parent, st));
+        }
+        ++rounds;
+        if ((rc = cc_compress(ctx, rounds))) return rc;
+        DevSpan span(st, "components.label");
+        HIP_TRY(k_fill_i64(minid, INT64_MAX, n, st));
+        HIP_TRY(k_level_prep(s.cnt, nullptr, 0, nullptr, st));
+        HIP_TRY(k_cc_min_id(parent, g.cc_tid, n, minid, st));
+        HIP_TRY(k_cc_label(parent, minid, n, label, &s.cnt->red[0], st));
+        span.end();
+        if ((rc = cc_word(ctx, true, components))) return rc;
+    } else {
+        const View pull = pull_view(g, TGO_SCOPE_BOTH_E);
+        HIP_TRY(hipMemcpyAsync(label, g.cc_tid, n * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        for (;;) {
+            HIP_TRY(k_level_prep(s.cnt, nullptr, 0, nullptr, st));
+            {
+                DevSpan span(st, "components.pull_round", {"round", rounds});
+                HIP_TRY(k_cc_pull_round(pull, n, label, &s.cnt->qlen, st));
+            }
+            ++rounds;
+            unsigned long long changed = 0;
+            if ((rc = cc_word(ctx, false, changed))) return rc;
+            if (!changed) break;
+        }
+        HIP_TRY(k_level_prep(s.cnt, nullptr, 0, nullptr, st));
+        HIP_TRY(k_cc_count_own(label, g.cc_tid, n, &s.cnt->red[0], st));
+        if ((rc = cc_word(ctx, true, components))) return rc;
+    }
+    HIP_TRY(hipEventRecord(ctx->ev1, st));
+    HIP_TRY(hipEventSynchronize(ctx->ev1));
+    trace_resolve(st);
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    ctx->st.last_kernel_ms = ms;
+    ctx->st.iterations = rounds;
+    if (info) *info = tgo_cc_info{static_cast<int64_t>(components), rounds, path};
+    if (label_out) {
+        HIP_TRY(k_unpermute_i64(label, g.perm, s.msg, n, st));
+        HIP_TRY(hipMemcpyAsync(label_out, s.msg, n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    ctx->res_kind = TGO_RESULT_COMPONENT;
+    ctx->res_empty = false;
+    ctx->res_src = ResultSource{label, nullptr};
+    return TGO_OK;
+}
+
+int tgo_copy_components(tgo_ctx* ctx, int64_t* label_out) {
+    if (!ctx || !label_out) return TGO_E_INVALID;
+    if (!ctx->loaded) return fail(ctx, TGO_E_STATE, "no graph loaded");
+    if (ctx->res_kind != TGO_RESULT_COMPONENT)
+        return fail(ctx, TGO_E_STATE, "tgo_components is not the last program run on this ctx");
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(k_unpermute_i64(ctx->sc.dist, ctx->g.perm, ctx->sc.msg, ctx->g.n, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(label_out, ctx->sc.msg, ctx->g.n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return TGO_OK;
+}
+
 int tgo_pagerank(tgo_ctx* ctx, const tgo_pr_args* a, double* pr_out) {
     if (!ctx) return TGO_E_INVALID;
     ctx->res_kind = -1;
@@ -2149,9 +2277,15 @@ static int result_rows_impl(tgo_ctx* ctx, const tgo_result_args* a, const Result
 int tgo_result_rows(tgo_ctx* ctx, const tgo_result_args* a, tgo_result_size* size, const tgo_rows_buf* out) {
     if (!ctx) return TGO_E_INVALID;
     if (!a || !size) return fail(ctx, TGO_E_INVALID, "null args");
-    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_DEGREE) return fail(ctx, TGO_E_INVALID, "invalid result kind");
+    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_COMPONENT || a->kind == TGO_RESULT_VALUES)
+        return fail(ctx, TGO_E_INVALID, "invalid result kind");
     if (ctx->res_kind != a->kind)
         return fail(ctx, TGO_E_STATE, "no finished program of that kind is the last one run on this ctx");
+    // a component label is a Titan id of the graph: an Integer key must be able to hold them all
+    if (a->kind == TGO_RESULT_COMPONENT && a->datatypes[0] == TGO_DT_INTEGER)
+        for (const int64_t id : ctx->titan_id)
+            if (id < INT32_MIN || id > INT32_MAX)
+                return fail(ctx, TGO_E_INVALID, "a value of an Integer compute key is out of int range");
     return result_rows_impl(ctx, a, ctx->res_src, ctx->res_empty, size, out);
 }
 

@@ -466,6 +466,7 @@ struct DevGraph {
     int32_t msc_hot = 0;
     int32_t msc_scope = -1;         // scope the layout was built for (-1: none yet)
     int64_t msc_req = 0;            // and its hot head
+    int64_t* cc_tid = nullptr;      // n: Titan id of every internal index (tgo_components, built on its first run)
 };
 
 // Multi-source BFS levels as bit planes: the level of (v, source r) is
@@ -825,6 +826,23 @@ int part_bfs_td_fused(tgo_ctx* ctx, int32_t level, uint64_t* disc, uint64_t* nb_
 int part_bfs_claim_remote(tgo_ctx* ctx, int32_t level, const uint64_t* recv, int32_t nslices, uint64_t* nb_local);
 int part_bfs_level_done(tgo_ctx* ctx);
 hipError_t k_unpermute_i32(const int32_t* in, const int32_t* perm, int32_t* out, int64_t n, hipStream_t s);
+
+// Connected components (cc.hip).  Hook path: parent (n, int32, internal ids, parent[x] <= x);
+// k_cc_hook unions every row with its entries [from, to) of one list (to < 0: the row's end);
+// k_cc_jump adds to *changed when a vertex was not yet directly under a root.
+hipError_t k_cc_init(int32_t* parent, int64_t n, hipStream_t s);
+hipError_t k_cc_hook(const DevCsr& list, int64_t n, int64_t from, int64_t to, int32_t* parent, hipStream_t s);
+hipError_t k_cc_jump(int32_t* parent, int64_t n, unsigned long long* changed, hipStream_t s);
+hipError_t k_cc_scatter_ids(const int64_t* row_ids, const int32_t* perm, int64_t* tid, int64_t n, hipStream_t s);
+// minid (n, INT64_MAX before): per root the smallest Titan id under it; label[v] = minid[root of v],
+// *roots += the number of roots
+hipError_t k_cc_min_id(const int32_t* parent, const int64_t* tid, int64_t n, int64_t* minid, hipStream_t s);
+hipError_t k_cc_label(const int32_t* parent, const int64_t* minid, int64_t n, int64_t* label, unsigned long long* roots,
+                      hipStream_t s);
+// Propagate path: one in-place MIN pull round over both lists (*changed += waves that lowered a
+// label); *roots += vertices whose label is their own id (= distinct labels at the fixed point)
+hipError_t k_cc_pull_round(const View& pull, int64_t n, int64_t* label, unsigned long long* changed, hipStream_t s);
+hipError_t k_cc_count_own(const int64_t* label, const int64_t* tid, int64_t n, unsigned long long* roots, hipStream_t s);
 
 // PageRank gather diagnostics: [diag_lo, diag_hi) = only sources in this range are gathered
 // (the others read as 0; results invalid) — attributes the update's time to source ranges.

@@ -43,7 +43,7 @@ __device__ inline uint64_t zigzag(int64_t v) {   // VariableLong.convert2Unsigne
 struct ResArgs {
     int kind;
     int vtype;              // TGO_RESULT_VALUES: TGO_VAL_INT64 / TGO_VAL_FP64
-    int vdt;                // TGO_RESULT_VALUES: the value's encoding (TGO_DT_LONG / INTEGER / DOUBLE)
+    int vdt;                // TGO_RESULT_VALUES / COMPONENT: the value's encoding (TGO_DT_LONG / INTEGER / DOUBLE)
     int nkeys;
     uint8_t hdr[2][12];     // column bytes of each key, in column order
     int hlen[2];
@@ -51,6 +51,12 @@ struct ResArgs {
     uint8_t lead[2];        // first value byte: 0x00 = the null flag of a typed key; a generic key's
                             // class registration (writePositive(13 / 20 / 12) = 0x8D / 0x94 / 0x8C)
     int64_t rel_base;
+    // how a value is written, decided once on the host from kind / vdt (the kernels branch on
+    // these two words only): varint = an Integer encoding (DEGREE, or an Integer key of a generic
+    // program / the component labels); flip = the sign-bit flip of a Long encoding
+    // (LongSerializer: v - Long.MIN_VALUE), 0 for the raw IEEE bits of a Double
+    int varint;
+    uint64_t flip;
 };
 
 // Value of slot `k` for internal vertex v; false when the vertex holds no such property.
@@ -65,6 +71,10 @@ __device__ inline bool value_of(const ResArgs& a, const void* v0, const void* v1
         bits = static_cast<uint64_t>(__double_as_longlong(x));
         return true;
     }
+    if (a.kind == TGO_RESULT_COMPONENT) {       // a label on every executed vertex
+        bits = static_cast<const uint64_t*>(v0)[v];
+        return true;
+    }
     if (a.kind == TGO_RESULT_VALUES) {          // v0: 8-byte values, v1: present flags
         bits = static_cast<const uint64_t*>(v0)[v];
         return static_cast<const uint8_t*>(v1)[v] != 0;
@@ -73,12 +83,8 @@ __device__ inline bool value_of(const ResArgs& a, const void* v0, const void* v1
     return true;
 }
 
-// Integer encodings: DEGREE, or a generic program's Integer key
-__device__ inline bool varint_value(const ResArgs& a) {
-    return a.kind == TGO_RESULT_DEGREE || (a.kind == TGO_RESULT_VALUES && a.vdt == TGO_DT_INTEGER);
-}
 __device__ inline int value_len(const ResArgs& a, uint64_t bits) {
-    if (varint_value(a)) return 1 + pos_len(zigzag(static_cast<int64_t>(bits)));
+    if (a.varint) return 1 + pos_len(zigzag(static_cast<int64_t>(bits)));
     return 9;
 }
 
@@ -129,11 +135,10 @@ __global__ void res_write(ResArgs a, const int32_t* perm, const void* v0, const 
         for (int i = 0; i < a.hlen[j]; ++i) *p++ = a.hdr[j][i];
         const int64_t vpos = p - ent;
         *p++ = a.lead[j];                              // null flag (typed key) or value class (generic key)
-        if (varint_value(a)) {
+        if (a.varint) {
             p = put_pos(p, zigzag(static_cast<int64_t>(bits)));
         } else {
-            const bool long_bits = a.kind == TGO_RESULT_DISTANCE || (a.kind == TGO_RESULT_VALUES && a.vdt == TGO_DT_LONG);
-            const uint64_t be = long_bits ? (bits ^ 0x8000000000000000ULL) : bits;
+            const uint64_t be = bits ^ a.flip;
             for (int i = 7; i >= 0; --i) *p++ = static_cast<uint8_t>(be >> (8 * i));
         }
         p = put_pos(p, static_cast<uint64_t>(a.rel_base + e0 + j));
@@ -178,10 +183,16 @@ int encode_results(const ResultSource& src, const tgo_result_args* a, const int3
     ra.kind = a->kind;
     ra.nkeys = a->kind == TGO_RESULT_PAGERANK ? 2 : 1;
     ra.rel_base = a->relation_id_base;
-    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_VALUES) { err = "unknown result kind"; return TGO_E_INVALID; }
-    int want[4][2] = {{TGO_DT_LONG, 0}, {TGO_DT_DOUBLE, TGO_DT_DOUBLE}, {TGO_DT_INTEGER, 0}, {0, 0}};
+    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_COMPONENT) { err = "unknown result kind"; return TGO_E_INVALID; }
+    int want[5][2] = {{TGO_DT_LONG, 0}, {TGO_DT_DOUBLE, TGO_DT_DOUBLE}, {TGO_DT_INTEGER, 0}, {0, 0}, {TGO_DT_LONG, 0}};
     // StandardSerializer registration numbers of the value classes (:71-81): Long 13, Double 20, Integer 12
-    uint8_t reg[4] = {0x80 | 13, 0x80 | 20, 0x80 | 12, 0};
+    uint8_t reg[5] = {0x80 | 13, 0x80 | 20, 0x80 | 12, 0, 0x80 | 13};
+    if (a->kind == TGO_RESULT_COMPONENT) {
+        // the labels are longs: a Long key, an Integer key (the caller checked the range) or a
+        // generic key holding Longs — the int64 encoder of a generic program's values
+        ra.vdt = a->datatypes[0] == TGO_DT_INTEGER ? TGO_DT_INTEGER : TGO_DT_LONG;
+        want[4][0] = ra.vdt;
+    }
     if (a->kind == TGO_RESULT_VALUES) {
         // a generic program's key: int64 values as a Long or Integer key (generic: Long),
         // fp64 values as a Double key (generic: Double)
@@ -199,14 +210,17 @@ int encode_results(const ResultSource& src, const tgo_result_args* a, const int3
             return TGO_E_INVALID;
         }
     }
+    const bool multi_dt = a->kind == TGO_RESULT_VALUES || a->kind == TGO_RESULT_COMPONENT;
+    ra.varint = a->kind == TGO_RESULT_DEGREE || (multi_dt && ra.vdt == TGO_DT_INTEGER);
+    ra.flip = a->kind == TGO_RESULT_DISTANCE || (multi_dt && ra.vdt == TGO_DT_LONG) ? 0x8000000000000000ULL : 0;
     uint8_t lead[2] = {0, 0};
     for (int k = 0; k < ra.nkeys; ++k) {
         if ((a->key_ids[k] & 63) != 5 || (a->key_ids[k] >> 6) <= 0) { err = "compute key is not a user property key id"; return TGO_E_INVALID; }
         if (a->datatypes[k] == TGO_DT_OBJECT) {
             lead[k] = reg[a->kind];                     // generic key: writeClassAndObject
         } else if (a->datatypes[k] != want[a->kind][k]) {
-            err = "compute key datatype must be Long (distance), Double (pageRank, edgeCount), Integer (degree) "
-                  "or generic (Object)";
+            err = "compute key datatype must be Long (distance), Double (pageRank, edgeCount), Integer (degree), "
+                  "Long or Integer (component) or generic (Object)";
             return TGO_E_UNSUPPORTED;
         }
     }

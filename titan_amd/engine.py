@@ -328,6 +328,22 @@ class Engine:
         _check(self.lib, self.ctx, self.lib.tgo_walkcount(self.ctx, int(k), L.ptr(out, C.c_int32)))
         return out
 
+    def components(self, fetch=True):
+        """Weakly connected components of a bothE load (tgo_components): (labels, info) —
+        labels[v] = the smallest Titan id of v's component, in row order (None when fetch is
+        False: they stay on the device for copy_components / result_rows); info = dict(components,
+        rounds, path).  rounds counts device rounds, not supersteps of the reference."""
+        a = L.CcArgs(L.SCOPE_BOTH_E, 0)
+        info = L.CcInfo()
+        out = np.zeros(self.n, dtype=np.int64) if fetch else None
+        _check(self.lib, self.ctx, self.lib.tgo_components(self.ctx, C.byref(a), L.ptr(out, C.c_int64), C.byref(info)))
+        return out, {"components": int(info.components), "rounds": int(info.rounds), "path": int(info.path)}
+
+    def copy_components(self):
+        out = np.zeros(self.n, dtype=np.int64)
+        _check(self.lib, self.ctx, self.lib.tgo_copy_components(self.ctx, L.ptr(out, C.c_int64)))
+        return out
+
     def result_rows(self, kind, key_ids, datatypes, relation_id_base):
         """Edgestore entries of the last program's compute keys (tgo_result_rows): the rows
         ResultMode PERSIST writes back (FulgoraGraphComputer.java:248-305)."""
