@@ -12,6 +12,7 @@ import pytest
 import fulgora as fr
 from conftest import load_fixture
 from generic_programs import ConnectedComponents, OracleEngine
+from ragged import edge_fixed_point, numpy_fixed_point
 from titan_amd import (ClusterCountMapReduce, ClusterPopulationMapReduce, ConnectedComponentVertexProgram, Engine,
                        FulgoraMemory, GpuGraph, Schema, TitanException, TitanGraphComputer, rmat_edges)
 from titan_amd import _lib as L
@@ -26,24 +27,6 @@ COMPONENT = ConnectedComponentVertexProgram.COMPONENT
 def reorder(ids_from, values, ids_to):
     pos = {int(v): i for i, v in enumerate(ids_from)}
     return np.array([values[pos[int(v)]] for v in ids_to], dtype=np.int64)
-
-
-def numpy_fixed_point(ids, recv, send):
-    """label[recv] = min(label[recv], label[send]) over every pull entry until nothing changes."""
-    lab = np.asarray(ids, np.int64).copy()
-    while True:
-        new = lab.copy()
-        np.minimum.at(new, recv, lab[send])
-        if np.array_equal(new, lab):
-            return lab
-        lab = new
-
-
-def edge_fixed_point(ids, src, dst):
-    """bothE pull lists of an edge list: a row pulls over its OUT and its IN entries."""
-    src = np.asarray(src, np.int64)
-    dst = np.asarray(dst, np.int64)
-    return numpy_fixed_point(ids, np.concatenate([src, dst]), np.concatenate([dst, src]))
 
 
 def rows_by_id(ids, src, dst):

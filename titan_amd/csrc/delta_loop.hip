@@ -702,7 +702,13 @@ __device__ __forceinline__ void relax_body(int64_t bid, int64_t nb, const int64_
                 ++ntake;
                 dtake += td[k];
             } else if (kBins) {
-                const int64_t ahead = cand[k] / delta - bucket;
+                // a merged range (decide_bins: buckets mlo .. bucket under one threshold) also
+                // improves pending vertices into its earlier buckets: they belong to the current
+                // pile — the ring slot of a bucket already passed is read as a later bucket's, the
+                // range would finish with the vertex still pending, and under the done filter a
+                // later single bucket would become final before that vertex relaxed into it
+                const int64_t past = cand[k] / delta - bucket;
+                const int64_t ahead = past < 0 ? 0 : past;
                 if (ahead >= nbins) {
                     spill = true;
                 } else {

@@ -4,6 +4,7 @@
 // (everything here is in an anonymous namespace, one copy per translation unit).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdlib>
 #include "engine.hpp"
 
 namespace tgo {
@@ -466,9 +467,17 @@ __device__ __forceinline__ void chunk_extract_live(int64_t words, const Live& li
 }
 
 // Grid for chunk_extract: >= 64 words per block, at most 2048 blocks.
+// TGO_EXTRACT_BLOCKS (1..2048, read once): a lower cap on the blocks, so that a small bitmap
+// gives a wave more than 64 words (the wide pass-2 forms: extract_write's `all`, the later
+// windows of live_words_plain); only the chunking changes, never what is extracted.
 inline int extract_grid(int64_t words) {
+    static const int64_t cap = [] {
+        const char* e = std::getenv("TGO_EXTRACT_BLOCKS");
+        const int64_t v = e ? std::atoll(e) : 2048;
+        return v >= 1 && v <= 2048 ? v : 2048;
+    }();
     const int64_t g = (words + 63) / 64;
-    return static_cast<int>(g < 1 ? 1 : (g > 2048 ? 2048 : g));
+    return static_cast<int>(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
 }  // namespace
