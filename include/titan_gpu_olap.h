@@ -348,8 +348,16 @@ int  tgo_copy_multi_distances(tgo_ctx* ctx, int32_t source, int64_t* dist_out);
 /* TGO_TUNE_DS_SMALL (binned delta SSSP without the done filter and pulls): 1 = the tiny steps
  * run in one block inside one launch (ds_small_steps), 0 = four grid launches per step;
  * -1 = TGO_DS_SMALL (default 0: measured slower).  Same distances either way. */
+/* TGO_TUNE_MS_STAY (tgo_bfs_multi): gamma >= 0 = after a pull level the next level pulls too
+ * while the list entries of the vertices still open for some source are at most gamma x the
+ * frontier's entries (0 = only the frontier's entries decide); -1 = TGO_MS_STAY or the default.
+ * TGO_TUNE_MS_SPARSE (tgo_bfs_multi): a fraction f >= 0 = level 0 and every push level whose
+ * frontier has at most f x (rows with entries) entries run in the sparse form (the touched
+ * vertices are queued by the push and settled from that queue, no pass over every mask);
+ * 0 = never; -1 = TGO_MS_SPARSE or the default.  Same distances either way. */
 enum { TGO_TUNE_MS_SPLIT = 1, TGO_TUNE_MS_GHOST = 2, TGO_TUNE_DS_BINS = 3, TGO_TUNE_DS_PILE_CAP = 4,
-       TGO_TUNE_DS_DONE = 5, TGO_TUNE_MS_COLD = 6, TGO_TUNE_DS_PULL = 7, TGO_TUNE_DS_SMALL = 8 };
+       TGO_TUNE_DS_DONE = 5, TGO_TUNE_MS_COLD = 6, TGO_TUNE_DS_PULL = 7, TGO_TUNE_DS_SMALL = 8,
+       TGO_TUNE_MS_STAY = 9, TGO_TUNE_MS_SPARSE = 10 };
 int  tgo_set_tuning(tgo_ctx* ctx, int32_t key, double value);
 
 /* ---- Tracing (the reference's only hook is FulgoraGraphComputer.java:143,307

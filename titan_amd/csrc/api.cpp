@@ -89,6 +89,8 @@ struct tgo_ctx {
     uint64_t* part_own_direct = nullptr;        // the last push did so (its settle skips the own OR)
     int64_t ms_cold = -1;       // tgo_set_tuning(TGO_TUNE_MS_COLD): 0 off, 1 on, > 1 on with that
                                 // hot head (and segment); < 0: TGO_MS_COLD / on
+    double ms_stay = -1.0;      // tgo_set_tuning(TGO_TUNE_MS_STAY): gamma; < 0: TGO_MS_STAY / the default
+    double ms_sparse = -1.0;    // tgo_set_tuning(TGO_TUNE_MS_SPARSE): fraction of n_active; < 0: TGO_MS_SPARSE / the default
     // state a native partitioned driver keeps between runs on this graph (part_driver.cpp:
     // the PageRank ghost lists); dropped with the graph
     std::shared_ptr<void> part_state;
@@ -636,8 +638,8 @@ int upload_graph(tgo_ctx* ctx, HostGraph& h, bool allow_segments = true) {
     if (!s.hcnt) {
         void* hp = nullptr;
         // fine-grained: the publish kernel's system-scope stores reach the spinning host
-        HIP_TRY(hipHostMalloc(&hp, sizeof(Counters) + 64, hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(hp, 0, sizeof(Counters) + 64);
+        HIP_TRY(hipHostMalloc(&hp, kPublishWords * 8, hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(hp, 0, kPublishWords * 8);
         s.hcnt = static_cast<Counters*>(hp);
         void* dp = nullptr;
         HIP_TRY(hipHostGetDevicePointer(&dp, hp, 0));
@@ -1268,7 +1270,7 @@ int finish_distance_program(tgo_ctx* ctx, int scope, int flags, int64_t* dist_ou
 
 // ============================================================================ C-ABI
 
-namespace tgo { double ms_split_of(const tgo_ctx* ctx); int part_upload(tgo_ctx* ctx, HostGraph& h, int64_t n_global, int64_t lo); }
+namespace tgo { double ms_split_of(const tgo_ctx* ctx); double ms_stay_of(const tgo_ctx* ctx); double ms_sparse_of(const tgo_ctx* ctx); int part_upload(tgo_ctx* ctx, HostGraph& h, int64_t n_global, int64_t lo); }
 
 namespace {
 struct TrimTemps {                  // tmp_cache.cpp: nothing stays reserved between loads
@@ -1319,6 +1321,16 @@ int tgo_set_tuning(tgo_ctx* ctx, int32_t key, double value) {
         if (!(value >= -1.0) || value >= 2147483647.0 || value != static_cast<double>(static_cast<int64_t>(value)))
             return fail(ctx, TGO_E_INVALID, "TGO_TUNE_MS_COLD: -1, 0, 1 or a hot-head size > 1");
         ctx->ms_cold = static_cast<int64_t>(value);
+        return TGO_OK;
+    case TGO_TUNE_MS_STAY:
+        if (!((value >= 0.0 && value <= 1.0e18) || value == -1.0))
+            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_MS_STAY: gamma >= 0 (0 = off) or -1 (the default)");
+        ctx->ms_stay = value;
+        return TGO_OK;
+    case TGO_TUNE_MS_SPARSE:
+        if (!((value >= 0.0 && value <= 1.0e18) || value == -1.0))
+            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_MS_SPARSE: a fraction >= 0 (0 = off) or -1 (the default)");
+        ctx->ms_sparse = value;
         return TGO_OK;
     case TGO_TUNE_DS_PILE_CAP:
         if (!(value >= 0.0) || value > 9.0e15) return fail(ctx, TGO_E_INVALID, "TGO_TUNE_DS_PILE_CAP: entries >= 0");
@@ -1694,7 +1706,11 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
     HIP_TRY(hipMemcpyAsync(s.ms_seeds, in.data(), nseeds * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(s.q[0], uniq.data(), uniq.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(s.ms_vis, 0, n * 8, st));
-    HIP_TRY(hipMemsetAsync(s.ms_fr, 0, n * 8, st));
+    // both mask buffers are still zero when the last sweep ended on an empty sparse level; the
+    // flag is down while a sweep runs, so a failed or depth-cut sweep leaves it down
+    const bool masks_zero = s.ms_masks_zero;
+    s.ms_masks_zero = false;
+    if (!masks_zero) HIP_TRY(hipMemsetAsync(s.ms_fr, 0, n * 8, st));
     s.ms_nplanes = 0;
     HIP_TRY(k_ms_seed(s.ms_seeds, nseeds, s.ms_vis, s.ms_fr, INT64_MAX, st));
     HIP_TRY(k_degree_i64(push, s.q[0], static_cast<int64_t>(uniq.size()), s.qdeg, st));
@@ -1716,6 +1732,13 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
     // TGO_MS_SPLIT: push budget of the pull levels' sparse sources, as a fraction of the
     // list entries (0 = every source pulled)
     const double split_frac = tgo::ms_split_of(ctx);
+    // TGO_TUNE_MS_STAY (gamma): after a pull level the next one pulls too while the list entries
+    // of the still-open vertices (mu, what a pull walks at most) are <= gamma x the frontier's
+    // entries (mf, what a push ORs atomically) — both directions pay one pass over the masks
+    // (the pull itself / ms_queue).  TGO_TUNE_MS_SPARSE: a push level whose frontier is queued
+    // and has at most that fraction of n_active entries (level 0 always) runs in the sparse
+    // form (k_ms_push_sparse / k_ms_settle_sparse): no pass over every mask.
+    const double stay_gamma = tgo::ms_stay_of(ctx), sparse_frac = tgo::ms_sparse_of(ctx);
     int64_t qlen = static_cast<int64_t>(uniq.size());
     int64_t mf = 0;             // the seeds' entries are not read back: level 0 always pushes (a
                                 // direction is policy only; the read cost a stream drain, ~45 us)
@@ -1732,14 +1755,22 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
     int cur = 0, levels = 0;
     bool queued = true;         // q[cur] holds the frontier (pull levels only count it)
     bool pulled = false;        // the previous level pulled
-    bool cnt_zero = false;      // the counters were zeroed after the last publish
+    bool cnt_zero = false;      // the counters are zero (k_publish_turn leaves them so)
+    bool nx_clean = masks_zero; // nx is zero over the active rows (no fill before a push)
+    int64_t prev_mf = 0;        // the entries of the frontier one level back
+    int64_t mu = -1;            // after a pull level: list entries of the still-open vertices (< 0: not counted)
+    bool level0_sparse = false, last_sparse = false;
+    unsigned long long se_pub[TGO_MAX_SOURCES] = {};   // the per-source entries the last settle published
+    const volatile unsigned long long* hw = reinterpret_cast<volatile unsigned long long*>(s.hcnt);
     for (int L = 0; L < depth && qlen > 0; ++L) {
-        const bool use_pull = static_cast<double>(mf) * ms_alpha > static_cast<double>(total);
+        const bool stay = pulled && mu >= 0 && stay_gamma > 0.0 &&
+                          static_cast<double>(mu) <= stay_gamma * static_cast<double>(mf);
+        const bool use_pull = stay || static_cast<double>(mf) * ms_alpha > static_cast<double>(total);
         DevSpan span(st, "msbfs.level", {"level", L}, {"pull", use_pull ? 1 : 0});
         if ((rc = ms_planes_for(ctx, L + 1))) return rc;
         const bool queued_before = queued;
         if (!use_pull && !queued) {     // the frontier's queue, for the push level's scan
-            HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), st));
+            if (!cnt_zero) HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), st));
             HIP_TRY(k_ms_queue(push, g.n_active, fr, s.q[cur], s.qdeg, s.cnt, st));
         }
         queued = !use_pull;
@@ -1747,8 +1778,11 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
         pulled = use_pull;
         bool sums = false;          // this push level's settle sums the per-source entries
         if (!use_pull && !queued_before) cnt_zero = false;      // ms_queue counted into them
+        bool sparse_level = false;  // this push level runs in the sparse form
+        bool count_open = false;    // this pull level counts mu
         if (use_pull) {
             if (!cnt_zero) HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), st));
+            cnt_zero = true;
             // Split the sources: the pull's walk of a vertex stops once every open source is
             // covered, and one source whose frontier never reaches the vertex (a source far
             // from it, or one whose sweep is over) makes every walk scan its whole list.  The
@@ -1761,21 +1795,26 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
             if (split_frac > 0.0 && !prev_pull) {
                 // every source's exact push entries in one pass, then the smallest within the budget
                 // after a push level its settle summed them already (srcent_ready)
-                if (!srcent_ready) HIP_TRY(k_ms_source_entries(push, fr, g.n_active, full, s.ms_srcent, st));
+                // (published with that level's counts: no copy, no stream synchronisation here)
                 static const bool srcent_check = env_double("TGO_MS_SRCENT_CHECK", 0.0) != 0.0;
                 if (srcent_ready && srcent_check) {     // dev check: the settle's sums = a pass of their own
                     HIP_TRY(k_ms_source_entries(push, fr, g.n_active, full, s.ms_stat, st));
-                    unsigned long long x[2][TGO_MAX_SOURCES];
-                    HIP_TRY(hipMemcpyAsync(x[0], s.ms_srcent, sizeof(x[0]), hipMemcpyDeviceToHost, st));
-                    HIP_TRY(hipMemcpyAsync(x[1], s.ms_stat, sizeof(x[1]), hipMemcpyDeviceToHost, st));
+                    unsigned long long x[TGO_MAX_SOURCES];
+                    HIP_TRY(hipMemcpyAsync(x, s.ms_stat, sizeof(x), hipMemcpyDeviceToHost, st));
                     HIP_TRY(hipStreamSynchronize(st));
-                    if (std::memcmp(x[0], x[1], sizeof(x[0])) != 0)
+                    if (std::memcmp(x, se_pub, sizeof(x)) != 0)
                         return fail(ctx, TGO_E_HIP, "multi-source BFS: settle per-source entries differ from ms_source_entries");
                     if (trace) std::fprintf(stderr, "[tgo] ms level %d: settle per-source entries checked\n", L);
                 }
                 unsigned long long se[TGO_MAX_SOURCES];
-                HIP_TRY(hipMemcpyAsync(se, s.ms_srcent, sizeof(se), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
+                if (srcent_ready) {
+                    std::memcpy(se, se_pub, sizeof(se));
+                } else {
+                    s.ms_srcent_zero = false;
+                    HIP_TRY(k_ms_source_entries(push, fr, g.n_active, full, s.ms_srcent, st));
+                    HIP_TRY(hipMemcpyAsync(se, s.ms_srcent, sizeof(se), hipMemcpyDeviceToHost, st));
+                    HIP_TRY(hipStreamSynchronize(st));
+                }
                 int order[TGO_MAX_SOURCES];
                 for (int r = 0; r < nseeds; ++r) order[r] = r;
                 std::sort(order, order + nseeds, [&](int a, int b) { return se[a] < se[b]; });
@@ -1791,13 +1830,13 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
                 if (sparse) {
                     bool any = false;
                     for (int r = 0; r < nseeds; ++r) any |= ((sparse >> r) & 1ULL) && se[r] > 0;
-                    HIP_TRY(hipMemsetAsync(nx, 0, g.n_active * 8, st));
+                    if (!nx_clean) HIP_TRY(hipMemsetAsync(nx, 0, g.n_active * 8, st));
                     if (any) {                           // push the sparse sources' frontiers
-                        HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), st));
                         HIP_TRY(k_ms_queue(push, g.n_active, fr, s.q[cur ^ 1], s.qdeg, s.cnt, st, sparse));
-                        if ((rc = read_counters(ctx))) return rc;
+                        const unsigned long long sseq = ++s.pub_seq;         // the counters zero again after it
+                        HIP_TRY(k_publish_turn(s.cnt, s.hcnt_dev, sseq, nullptr, st));
+                        if ((rc = wait_publish(ctx, sseq))) return rc;
                         const int64_t sq = static_cast<int64_t>(s.hcnt->qlen);
-                        HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), st));
                         if (sq > 0) {
                             if ((rc = scan_frontier(ctx, sq))) return rc;
                             HIP_TRY(k_ms_push(push, s.q[cur ^ 1], s.qpre, sq, fr, s.ms_vis, nx, st, PackTouch{}, sparse));
@@ -1827,9 +1866,15 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
                     cs.need = s.ms_need;
                 }
             }
+            // mu for the next level's direction.  The rows a cold split leaves to ms_finish are
+            // not in it: no stay rule after such a level.  Counted once the frontier shrinks (mf
+            // below the level before), since only then can the next level fall under the push
+            // threshold: the count is one more atomic per block, 9 - 25 us at RMAT-24's two
+            // large levels.
+            count_open = stay_gamma > 0.0 && !cs.acc && mf < prev_mf;
             HIP_TRY(k_ms_pull(pull, push, g.n_active, full, fr, filter ? s.ms_fbm : nullptr, s.ms_vis, nx,
                               ms_planes(ctx), s.cnt, L + 1, st, filter ? filter_from : 0, full & ~sparse,
-                              sparse ? nx : nullptr, cs));
+                              sparse ? nx : nullptr, cs, count_open));
             if (cs.acc) {
                 HIP_TRY(k_ms_cold(g.msc_adj, g.msc_row, g.msc_C, fr, s.ms_need, s.ms_cacc, st));
                 HIP_TRY(k_ms_finish(push, g.n_active, full, s.ms_vis, nx, sparse ? nx : nullptr, ms_planes(ctx), s.cnt,
@@ -1839,7 +1884,10 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
             // candidates only land on rows with entries (< n_active); the tail is never read
             // one kernel zeroes the counters, the candidate masks and the scan's tail entry
             // (three fills of ~5 us launch each before)
-            HIP_TRY(k_level_prep(s.cnt, nx, g.n_active, s.qdeg + qlen, st));
+            // (the counters only when a queue build counted into them, the masks only when nx
+            // is not known to be zero: after a dense push or a pull)
+            HIP_TRY(k_level_prep(cnt_zero ? nullptr : s.cnt, nx, nx_clean ? 0 : g.n_active, s.qdeg + qlen, st));
+            cnt_zero = true;
             // A small frontier of long lists pushes target-ranged (k_ms_push_ranged: XCD x on
             // the x-th eighth of the (target range, entry) enumeration, its ranges' masks in
             // its L2); TGO_MS_PUSH_RANGE = log2 of the range (0 = off).
@@ -1847,6 +1895,11 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
             const int64_t nr = (g.n_active + rng - 1) / rng;
             const bool ranged = push_range_log2 > 0 && mf >= push_range_min && nr > 1 &&
                                 (nr + 1) * qlen <= kMsRangePairs && nr * qlen + 1 <= n + 2;
+            // the sparse form: the frontier (queued, as for every push) has little to push (the
+            // ranged push is for large frontiers and does not combine with it)
+            sparse_level = sparse_frac > 0.0 && !ranged &&
+                           (L == 0 || static_cast<double>(mf) <= sparse_frac * static_cast<double>(g.n_active));
+            sums = split_frac > 0.0 && (L == 0 || static_cast<double>(mf) * ms_alpha * 64.0 > static_cast<double>(total));
             if (ranged) {
                 for (int b = 0; b < 2; ++b)
                     if (!s.ms_rp[b]) HIP_TRY(dev_alloc(ctx, s.ms_rp[b], kMsRangePairs));
@@ -1855,6 +1908,9 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
                                          s.cub_tmp, s.cub_bytes, fr, light ? nullptr : s.ms_vis, nx, st));
             } else {
             HIP_TRY(scan_exclusive_i64(s.cub_tmp, s.cub_bytes, s.qdeg, s.qpre, qlen + 1, st));   // tail zeroed above
+            if (sparse_level)
+                HIP_TRY(k_ms_push_sparse(push, s.q[cur], s.qpre, qlen, fr, s.ms_vis, nx, s.q[cur ^ 1], s.cnt, st));
+            else {
             // While few vertices are reached the push skips the reached-mask read of its
             // targets (ms_settle drops the reached bits anyway): one random 8-byte read less
             // per entry at the second level's 12.7 M entries (RMAT-24).  TGO_MS_PUSH_PROBE=0
@@ -1863,16 +1919,20 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
             HIP_TRY(k_ms_push(push, s.q[cur], s.qpre, qlen, fr, light ? nullptr : s.ms_vis, nx, st, PackTouch{}, ~0ULL,
                               light ? push_probe : true));
             }
+            }
             // the new frontier's push entries per source, for the next level's split — when that
             // level may pull (this frontier's entries within 64x of the pull threshold; a
             // frontier grows at most ~40x a level on RMAT-24), else the split computes them
             // (level 0: the seeds' entries are not known, so always)
-            sums = split_frac > 0.0 && (L == 0 || static_cast<double>(mf) * ms_alpha * 64.0 > static_cast<double>(total));
-            if (sums) HIP_TRY(hipMemsetAsync(s.ms_srcent, 0, 64 * sizeof(unsigned long long), st));
+            if (sums && !s.ms_srcent_zero) HIP_TRY(hipMemsetAsync(s.ms_srcent, 0, 64 * sizeof(unsigned long long), st));
+            if (sums) s.ms_srcent_zero = false;
             // a frontier within 8x of the pull threshold: the next level will likely pull and
             // needs no queue — settle and count only (ms_queue builds it if the level pushes)
             const bool next_pull = static_cast<double>(mf) * ms_alpha * 8.0 > static_cast<double>(total);
-            if (next_pull) {
+            if (sparse_level) {
+                HIP_TRY(k_ms_settle_sparse(push, s.q[cur ^ 1], s.qdeg, s.ms_vis, nx, ms_planes(ctx), s.cnt, L + 1, st,
+                                           sums ? s.ms_srcent : nullptr, s.q[cur], qlen, fr));
+            } else if (next_pull) {
                 HIP_TRY(k_ms_settle_count(push, g.n_active, s.ms_vis, nx, ms_planes(ctx), s.cnt, L + 1, st,
                                           sums ? s.ms_srcent : nullptr));
                 queued = false;
@@ -1886,20 +1946,29 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
             // publish the counts, then queue the next level's direction-independent prefix (its
             // level planes, zeroed counters) before the host waits: the GPU runs it during the
             // host's round trip (≈ 10–25 us a level)
+            // (the same launch zeroes the counters, and publishes and zeroes the per-source sums)
             const unsigned long long seq = ++s.pub_seq;
-            HIP_TRY(k_publish_counters(s.cnt, s.hcnt_dev, seq, st));
-            if (L + 1 < depth) {
-                if ((rc = ms_planes_for(ctx, L + 2))) return rc;
-                HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), st));
-                cnt_zero = true;
-            }
+            HIP_TRY(k_publish_turn(s.cnt, s.hcnt_dev, seq, sums ? s.ms_srcent : nullptr, st));
+            cnt_zero = true;
+            if (sums) s.ms_srcent_zero = true;
+            if (L + 1 < depth && (rc = ms_planes_for(ctx, L + 2))) return rc;
             if ((rc = wait_publish(ctx, seq))) return rc;
         }
         qlen = static_cast<int64_t>(s.hcnt->qlen);
+        prev_mf = mf;
         mf = static_cast<int64_t>(s.hcnt->mf);
+        mu = count_open ? static_cast<int64_t>(s.hcnt->open) : -1;
+        if (sums)
+            for (int r = 0; r < TGO_MAX_SOURCES; ++r) se_pub[r] = hw[kPublishExtra + r];
         reached += qlen;
-        if (trace) std::fprintf(stderr, "[tgo] ms level %d %s -> %lld vertices, %lld entries, %llu source-bits\n", L,
-                                use_pull ? "pull" : "push", (long long)qlen, (long long)mf, s.hcnt->red[0]);
+        // the consumed frontier's masks were cleared by the sparse settle: zero when they are nx
+        nx_clean = sparse_level;
+        last_sparse = sparse_level;
+        if (L == 0) level0_sparse = sparse_level;
+        if (trace) std::fprintf(stderr, "[tgo] ms level %d %s -> %lld vertices, %lld entries, %llu source-bits%s\n", L,
+                                use_pull ? "pull" : "push", (long long)qlen, (long long)mf, s.hcnt->red[0],
+                                use_pull ? (stay ? " (stayed in pull)" : "") : (sparse_level ? " (sparse)" : ""));
+        if (trace && count_open) std::fprintf(stderr, "[tgo]   %lld list entries of still-open vertices\n", (long long)mu);
         static const bool diag = env_double("TGO_MS_DIAG", 0.0) != 0.0;
         if (trace && diag && use_pull) {
             unsigned long long d[10] = {};
@@ -1922,6 +1991,9 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
     ctx->st.last_kernel_ms = ms;
     ctx->st.levels = levels;
     ctx->st.iterations = a->max_depth;
+    // the last level was sparse and found nothing: its frontier's masks are cleared, nothing was
+    // written to the other buffer; ms_fr's entry-less tail (seeds only) was cleared at level 0
+    s.ms_masks_zero = level0_sparse && last_sparse && qlen == 0;
     if (a->flags & TGO_FLAG_STATS) {
         HIP_TRY(hipMemsetAsync(s.ms_stat, 0, 2 * TGO_MAX_SOURCES * sizeof(unsigned long long), st));
         HIP_TRY(k_ms_reach(pull, s.ms_vis, n, nseeds, s.ms_stat, s.ms_stat + TGO_MAX_SOURCES, st));
@@ -3936,6 +4008,16 @@ int part_scratch(tgo_ctx* ctx, void** p, int64_t bytes, int slot) {
 double ms_split_of(const tgo_ctx* ctx) {
     static const double env = env_double("TGO_MS_SPLIT", 0.005);
     return ctx->ms_split >= 0.0 ? ctx->ms_split : env;
+}
+// gamma of the stay-in-pull rule and the sparse push levels' fraction of n_active (tgo_bfs_multi):
+// the ctx's tgo_set_tuning value, else TGO_MS_STAY / TGO_MS_SPARSE, else the defaults.
+double ms_stay_of(const tgo_ctx* ctx) {
+    static const double env = std::max(0.0, env_double("TGO_MS_STAY", kMsStayDefault));
+    return ctx->ms_stay >= 0.0 ? ctx->ms_stay : env;
+}
+double ms_sparse_of(const tgo_ctx* ctx) {
+    static const double env = std::max(0.0, env_double("TGO_MS_SPARSE", kMsSparseDefault));
+    return ctx->ms_sparse >= 0.0 ? ctx->ms_sparse : env;
 }
 
 }  // namespace tgo

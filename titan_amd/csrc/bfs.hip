@@ -474,6 +474,27 @@ hipError_t k_level_turn(Counters* c, unsigned long long* host, unsigned long lon
     level_turn<<<grid_for(std::max<int64_t>(words, kCounterWords)), kBlock, 0, s>>>(c, host, seq, clear, words, qdeg);
     return hipGetLastError();
 }
+// publish_counters that leaves the counters zero for the next kernel that counts (level_turn's
+// end without its bitmap): no memset dispatch after the publish.  src64 (optional): 64 more
+// device words (the multi-source sweep's per-source entry sums) published to the host words
+// from kPublishExtra on and zeroed the same way.
+__global__ void publish_turn(Counters* c, unsigned long long* host, unsigned long long seq, unsigned long long* src64) {
+    const int i = threadIdx.x;
+    unsigned long long* w = reinterpret_cast<unsigned long long*>(c);
+    if (i < kCounterWords) __hip_atomic_store(&host[i], w[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (src64 && i < 64) __hip_atomic_store(&host[kPublishExtra + i], src64[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __threadfence_system();
+    __syncthreads();                          // every word read before any is zeroed
+    if (i == 0) __hip_atomic_store(&host[kCounterWords], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (i < kCounterWords) w[i] = 0;
+    if (src64 && i < 64) src64[i] = 0;
+}
+hipError_t k_publish_turn(Counters* c, unsigned long long* host, unsigned long long seq, unsigned long long* src64,
+                          hipStream_t s) {
+    static_assert(kCounterWords <= 64, "publish_turn: one wave covers the counters");
+    publish_turn<<<1, 64, 0, s>>>(c, host, seq, src64);
+    return hipGetLastError();
+}
 hipError_t k_publish_counters(const Counters* c, unsigned long long* host, unsigned long long seq, hipStream_t s) {
     publish_counters<<<1, 64, 0, s>>>(c, host, seq);
     return hipGetLastError();

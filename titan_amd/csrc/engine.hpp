@@ -484,7 +484,10 @@ struct Counters {               // device-side level counters (one cache line ea
     unsigned long long mf;      // sum of push degrees of the next frontier
     unsigned long long pad1[7];
     unsigned long long err;     // program failure flag
-    unsigned long long pad2[7];
+    unsigned long long open;    // multi-source pull: list entries of the vertices still open (a line
+                                // away from red[]: one more atomic per block on that line showed
+                                // as +56 us at RMAT-24's short fourth level)
+    unsigned long long pad2[6];
     unsigned long long red[2];  // reductions (reached vertices, reached entries)
     unsigned long long red2;    // third reduction (delta-stepping: bucket members left)
     unsigned long long pad3[5];
@@ -575,6 +578,8 @@ struct Scratch {
     uint64_t* ms_nx = nullptr;      // n: next-frontier mask
     uint64_t* ms_lvl = nullptr;     // kLevelPlanes x n: bit r of plane k = bit k of source r's level
     int32_t ms_nplanes = 0;         // planes zeroed (and valid) in the current sweep
+    bool ms_masks_zero = false;     // ms_fr and ms_nx are all zero (the last sweep ended on an empty sparse level)
+    bool ms_srcent_zero = false;    // ms_srcent is zero (published and zeroed by k_publish_turn)
     int64_t* ms_seeds = nullptr;    // 64
     unsigned long long* ms_stat = nullptr;   // 128: reached[64], entries[64]
     int32_t ms_nsrc = 0;
@@ -630,6 +635,14 @@ hipError_t k_publish_counts(const Counters* c, int64_t* out, int64_t* slot, hipS
 // host-mapped mirror, then the sequence number after them (system scope); the host spins on it.
 constexpr int kCounterWords = static_cast<int>(sizeof(Counters) / 8);
 hipError_t k_publish_counters(const Counters* c, unsigned long long* host, unsigned long long seq, hipStream_t s);
+// The host mirror's words: [0, kCounterWords) the counters, kCounterWords the sequence number,
+// [kPublishExtra, kPublishExtra + 64) the extra words of k_publish_turn.
+constexpr int kPublishExtra = kCounterWords + 8;
+constexpr int kPublishWords = kPublishExtra + 64;
+// k_publish_counters, then the counters zeroed in the same launch; src64 (may be null): 64 device
+// words published to the extra host words and zeroed with them.
+hipError_t k_publish_turn(Counters* c, unsigned long long* host, unsigned long long seq, unsigned long long* src64,
+                          hipStream_t s);
 // `count` (<= kCounterWords) device words published like the counters (partitioned drivers)
 // The delta loop's done / err / spill flags to host-mapped words 0..2 and the sequence number.
 hipError_t k_ds_publish(const DsLoop* L, unsigned long long* host, unsigned long long seq, hipStream_t s);
@@ -753,7 +766,7 @@ hipError_t k_ms_diag_take(unsigned long long* out10, hipStream_t s);   // 10 dia
 hipError_t k_ms_pull(const View& pull, const View& push, int64_t n_active, uint64_t full, const uint64_t* fr,
                      const uint64_t* fbm, uint64_t* vis, uint64_t* nx, LevelPlanes lvl, Counters* cnt,
                      int32_t next_level, hipStream_t s, int32_t filter_from, uint64_t dense = ~0ULL,
-                     const uint64_t* cand = nullptr, MsColdSplit cs = MsColdSplit());
+                     const uint64_t* cand = nullptr, MsColdSplit cs = MsColdSplit(), bool count_open = false);
 // the blocked cold pass and the settle of the rows it completed (msbfs.hip)
 hipError_t k_ms_cold(const int32_t* cadj, const int32_t* crow, int64_t C, const uint64_t* fr, const uint8_t* need,
                      uint64_t* acc, hipStream_t s);
@@ -783,6 +796,19 @@ struct PackTouch { uint8_t* flag = nullptr; int64_t n_local = 1; int64_t cps = 1
 hipError_t k_ms_push(const View& push, const int32_t* q, const int64_t* qpre, int64_t qlen, const uint64_t* fr,
                      const uint64_t* vis, uint64_t* nx, hipStream_t s, PackTouch touch = {}, uint64_t mask = ~0ULL,
                      bool probe = true, uint64_t* own_nx = nullptr, int64_t own_lo = 0);
+// Defaults of TGO_TUNE_MS_STAY (gamma of the stay-in-pull rule) and TGO_TUNE_MS_SPARSE (a push
+// level with at most this fraction of n_active entries runs sparse): DESIGN.md §4.1.
+constexpr double kMsStayDefault = 4.0;
+constexpr double kMsSparseDefault = 1.0 / 16.0;
+// Sparse push level (one GPU): nx all zero beforehand; the touched vertices — exactly the next
+// frontier — are appended to qn (length in cnt->qlen, no particular order), and
+// k_ms_settle_sparse settles them over that list (length read on the device): vis, levels,
+// qdeg, cnt->mf / red[0], srcent; it also zeroes fr at the consumed queue qp[0, qplen).
+hipError_t k_ms_push_sparse(const View& push, const int32_t* q, const int64_t* qpre, int64_t qlen, const uint64_t* fr,
+                            const uint64_t* vis, uint64_t* nx, int32_t* qn, Counters* cnt, hipStream_t s);
+hipError_t k_ms_settle_sparse(const View& push, const int32_t* qn, int64_t* qdeg, uint64_t* vis, const uint64_t* nx,
+                              LevelPlanes lvl, Counters* cnt, int32_t next_level, hipStream_t s,
+                              unsigned long long* srcent, const int32_t* qp, int64_t qplen, uint64_t* fr);
 constexpr int64_t kMsRangePairs = int64_t(1) << 22;   // ranged push: (entry, range) bounds per list
 // Target-ranged push of a small frontier (msbfs.hip): pairs (range of S targets, entry) in
 // range-major order, XCD x on the x-th eighth; P0 / P1 hold qlen * (R + 1), cnt / pre R * qlen + 1.

@@ -39,22 +39,29 @@ __device__ __forceinline__ void record_level(int64_t v, uint64_t fresh, int32_t 
 // entries, source bits) reduced over the block, one atomicAdd per block and counter.  No
 // per-word block barrier: a pull level's waves finish their words independently (lists are
 // skewed; a barrier per word made every wave wait for the block's longest list).
+// mu (ms_pull with count_open): pull-list entries of the vertices still open after the level,
+// into cnt->open.
 __device__ __forceinline__ void count_flush(Counters* cnt, unsigned long long nv, unsigned long long mf,
-                                            unsigned long long bits) {
-    __shared__ unsigned long long s_nv[kWavesPerBlock], s_mf[kWavesPerBlock], s_bits[kWavesPerBlock];
+                                            unsigned long long bits, unsigned long long mu = 0) {
+    __shared__ unsigned long long s_nv[kWavesPerBlock], s_mf[kWavesPerBlock], s_bits[kWavesPerBlock], s_mu[kWavesPerBlock];
     for (int off = 32; off > 0; off >>= 1) {
         nv += __shfl_xor(nv, off, 64);
         mf += __shfl_xor(mf, off, 64);
         bits += __shfl_xor(bits, off, 64);
+        mu += __shfl_xor(mu, off, 64);
     }
-    if (lane() == 0) { s_nv[threadIdx.x >> 6] = nv; s_mf[threadIdx.x >> 6] = mf; s_bits[threadIdx.x >> 6] = bits; }
+    if (lane() == 0) {
+        s_nv[threadIdx.x >> 6] = nv; s_mf[threadIdx.x >> 6] = mf; s_bits[threadIdx.x >> 6] = bits;
+        s_mu[threadIdx.x >> 6] = mu;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        unsigned long long a = 0, m = 0, c = 0;
-        for (int w = 0; w < kWavesPerBlock; ++w) { a += s_nv[w]; m += s_mf[w]; c += s_bits[w]; }
+        unsigned long long a = 0, m = 0, c = 0, u = 0;
+        for (int w = 0; w < kWavesPerBlock; ++w) { a += s_nv[w]; m += s_mf[w]; c += s_bits[w]; u += s_mu[w]; }
         if (a) atomicAdd(&cnt->qlen, a);
         if (m) atomicAdd(&cnt->mf, m);
         if (c) atomicAdd(&cnt->red[0], c);
+        if (u) atomicAdd(&cnt->open, u);
     }
 }
 
@@ -104,13 +111,15 @@ __device__ unsigned long long g_ms_diag[kDiagWords];
 // written (ms_cold ORs its cold neighbours in, ms_finish settles it).
 // kRamp: a long list's first trip reads 64 entries only (its head of hubs often covers every
 // open source), the later ones kLong * 64.
+// count_open: also sum the list entries of the vertices still open after the level (cnt->open; the
+// rows a cold split leaves to ms_finish are not in it).
 template <int kStep, bool kDiag = false, int kLong = 4, bool kRamp = false>
 __global__ void __launch_bounds__(kBlock) ms_pull(View pull, View push, int64_t n_active, uint64_t full,
         const uint64_t* __restrict__ fr, const uint64_t* __restrict__ fbm, uint64_t* __restrict__ vis,
         uint64_t* __restrict__ nx, LevelPlanes lvl, Counters* cnt, int32_t next_level, int32_t filter_from,
-        uint64_t dense, const uint64_t* __restrict__ cand, MsColdSplit cs, int64_t coop) {
+        uint64_t dense, const uint64_t* __restrict__ cand, MsColdSplit cs, int64_t coop, bool count_open) {
     const int32_t hot_lim = cs.hot_lim;
-    unsigned long long nv = 0, mf = 0, bits = 0;
+    unsigned long long nv = 0, mf = 0, bits = 0, mu = 0;
     unsigned long long dg[kDiagWords] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const int64_t words = (n_active + 63) >> 6;
     // wave w of the block takes word b + w; words past the end run as all-closed lanes.  No
@@ -244,6 +253,8 @@ __global__ void __launch_bounds__(kBlock) ms_pull(View pull, View push, int64_t 
             mf += static_cast<unsigned long long>(push_degree(push, v));
             bits += static_cast<unsigned long long>(__popcll(fresh));
         }
+        // still open after this level: its list is what a pull of the next level walks
+        if (count_open && (open & ~fresh)) mu += static_cast<unsigned long long>(deg);
     }
     if (kDiag) {
         for (int i = 0; i < kDiagWords; ++i) {
@@ -252,7 +263,7 @@ __global__ void __launch_bounds__(kBlock) ms_pull(View pull, View push, int64_t 
             if (lane() == 0 && x) atomicAdd(&g_ms_diag[i], x);
         }
     }
-    count_flush(cnt, nv, mf, bits);
+    count_flush(cnt, nv, mf, bits, mu);
 }
 
 // Blocked cold pass of a split pull level: the cold entries (neighbour >= hot_lim) of every row,
@@ -473,11 +484,17 @@ constexpr int kPushLds = 514;
 // kE: edges per thread (a tile is kBlock * kE edges).  4 (round 5): 50 VGPRs, 8 waves per SIMD
 // — the RMAT-24 sweep 3.76 -> 3.68 ms against 8 (86 VGPRs, 5 waves;
 // profiles/r05ms1_ms_push_e_ab.log); TGO_MS_PUSH_E=8 for the A/B
-template <int kE = 4>
+// kSparse (ms_push_sparse, a level with little to do; one GPU): nx is all zero beforehand, every
+// contribution is masked with ~vis[v] and the OR returns the old word, so exactly one thread
+// sees 0 for each touched vertex and appends it to the next queue qn (slots from cnt->qlen, one
+// atomicAdd per wave and stage).  The touched list is exactly the next frontier and nx[v]
+// holds only fresh bits: ms_settle_sparse settles it without a pass over every mask.  The
+// queue is in no particular order (nothing downstream of it needs one).
+template <int kE = 4, bool kSparse = false>
 __global__ void __launch_bounds__(kBlock) ms_push(View push, const int32_t* __restrict__ q,
         const int64_t* __restrict__ qpre, int64_t qlen, const uint64_t* __restrict__ fr,
         const uint64_t* __restrict__ vis, uint64_t* __restrict__ nx, PackTouch touch, uint64_t mask, bool probe,
-        uint64_t* __restrict__ own_nx, int64_t own_lo) {
+        uint64_t* __restrict__ own_nx, int64_t own_lo, int32_t* __restrict__ qn, Counters* cnt) {
     __shared__ int64_t s_pre[kPushLds];
     __shared__ int64_t s_b0[kPushLds];     // list 0 begin
     __shared__ int64_t s_b1[kPushLds];     // list 1 begin minus list 0's length (o >= d0 reads adj1[s_b1 + o])
@@ -562,6 +579,25 @@ __global__ void __launch_bounds__(kBlock) ms_push(View push, const int32_t* __re
             if (vis) cv[k] = vis[v[k]];
             if (probe) cn[k] = *tgt[k];
         }
+        if constexpr (kSparse) {
+#pragma unroll
+            for (int k = 0; k < kE; ++k) {       // 4: the returning atomic, then the wave's append
+                bool first = false;
+                if (v[k] >= 0) {
+                    const uint64_t mk = m[k] & ~cv[k];
+                    if (mk && (cn[k] & mk) != mk)
+                        first = atomicOr(reinterpret_cast<unsigned long long*>(tgt[k]), mk) == 0ULL;
+                }
+                const unsigned long long bal = __ballot(first);
+                if (bal) {                        // wave-uniform
+                    const int lead = __ffsll(static_cast<long long>(bal)) - 1;
+                    unsigned long long base = 0;
+                    if (lane() == lead) base = atomicAdd(&cnt->qlen, static_cast<unsigned long long>(__popcll(bal)));
+                    base = __shfl(base, lead, 64);
+                    if (first) qn[base + __popcll(bal & ((1ULL << lane()) - 1ULL))] = v[k];
+                }
+            }
+        } else {
 #pragma unroll
         for (int k = 0; k < kE; ++k) {           // 4: the atomic
             if (v[k] < 0) continue;
@@ -572,8 +608,44 @@ __global__ void __launch_bounds__(kBlock) ms_push(View push, const int32_t* __re
                     touch.flag[(v[k] / touch.n_local) * touch.cps + (v[k] % touch.n_local) / kPackChunk] = 1;
             }
         }
+        }
         __syncthreads();
     }
+}
+
+// The settle of a sparse push level (ms_push<.., true>): over the touched list qn, whose length
+// is read on the device (cnt->qlen, complete: the push finished).  nx[v] holds only fresh bits:
+// vis |= fresh, the level recorded, qdeg[i] for the next level's scan, and the counts (entries,
+// source bits, per-source sums when asked; the vertex count is the list's length already).
+// It also clears fr[u] of the consumed queue qp[0, qplen) — every vertex of the frontier —
+// so the buffer that becomes nx after the swap is zero without a fill.
+__global__ void __launch_bounds__(kBlock) ms_settle_sparse(View push, const int32_t* __restrict__ qn,
+        int64_t* __restrict__ qdeg, uint64_t* __restrict__ vis, const uint64_t* __restrict__ nx, LevelPlanes lvl,
+        Counters* cnt, int32_t next_level, unsigned long long* __restrict__ srcent, const int32_t* __restrict__ qp,
+        int64_t qplen, uint64_t* __restrict__ fr) {
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+    const int64_t t0 = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    for (int64_t i = t0; i < qplen; i += stride) fr[qp[i]] = 0;
+    const int64_t len = static_cast<int64_t>(cnt->qlen);
+    unsigned long long mf = 0, bits = 0, ssum = 0;
+    for (int64_t b = t0 - lane(); b < len; b += stride) {          // wave-uniform trips
+        const int64_t i = b + lane();
+        uint64_t fresh = 0;
+        int64_t deg = 0;
+        if (i < len) {
+            const int32_t v = qn[i];
+            fresh = nx[v];
+            vis[v] |= fresh;
+            record_level(v, fresh, next_level, lvl);
+            deg = push_degree(push, v);
+            qdeg[i] = deg;
+            mf += static_cast<unsigned long long>(deg);
+            bits += static_cast<unsigned long long>(__popcll(fresh));
+        }
+        if (srcent && __ballot(fresh != 0)) source_columns_add(fresh, static_cast<unsigned long long>(deg), ssum);
+    }
+    count_flush(cnt, 0, mf, bits);
+    if (srcent) source_sums_flush(ssum, srcent);                 // grid-uniform
 }
 
 // Target-ranged push (a small frontier of long lists, e.g. RMAT-24's second level: 1355
@@ -972,7 +1044,7 @@ hipError_t k_ms_seed(const int64_t* seeds, int nseeds, uint64_t* vis, uint64_t* 
 hipError_t k_ms_pull(const View& pull, const View& push, int64_t n_active, uint64_t full, const uint64_t* fr,
                      const uint64_t* fbm, uint64_t* vis, uint64_t* nx, LevelPlanes lvl, Counters* cnt,
                      int32_t next_level, hipStream_t s, int32_t filter_from, uint64_t dense, const uint64_t* cand,
-                     MsColdSplit cs) {
+                     MsColdSplit cs, bool count_open) {
     // TGO_MS_STEP: entries a lane loads per round trip of its own list (4 default since the
     // trips are branch-free, round 6: sweep 3.623 -> 3.562 ms against 8 with the branchy trips,
     // profiles/r06ms1_ms_branchfree_ab.log; 8 / 16 probes)
@@ -988,7 +1060,7 @@ hipError_t k_ms_pull(const View& pull, const View& push, int64_t n_active, uint6
     static const int64_t coop = [] { const char* e = std::getenv("TGO_MS_COOP"); return e ? std::atoll(e) : kCoop; }();
     const dim3 grid(grid_for(n_active, 8192));
 #define TGO_MS_PULL(S, D, LG, R) ms_pull<S, D, LG, R><<<grid, kBlock, 0, s>>>(pull, push, n_active, full, fr, fbm, vis, \
-        nx, lvl, cnt, next_level, filter_from, dense, cand, cs, coop)
+        nx, lvl, cnt, next_level, filter_from, dense, cand, cs, coop, count_open)
     if (diag) TGO_MS_PULL(8, true, 1, false);
     else if (ramp) TGO_MS_PULL(8, false, 4, true);
     else if (step == 4 && lng == 1) TGO_MS_PULL(4, false, 1, false);
@@ -1067,8 +1139,23 @@ hipError_t k_ms_push(const View& push, const int32_t* q, const int64_t* qpre, in
                      const uint64_t* vis, uint64_t* nx, hipStream_t s, PackTouch touch, uint64_t mask, bool probe,
                      uint64_t* own_nx, int64_t own_lo) {
     static const bool e8 = [] { const char* e = std::getenv("TGO_MS_PUSH_E"); return e && std::atoi(e) == 8; }();
-    if (e8) ms_push<8><<<256 * 8, kBlock, 0, s>>>(push, q, qpre, qlen, fr, vis, nx, touch, mask, probe, own_nx, own_lo);
-    else ms_push<><<<256 * 8, kBlock, 0, s>>>(push, q, qpre, qlen, fr, vis, nx, touch, mask, probe, own_nx, own_lo);
+    if (e8) ms_push<8><<<256 * 8, kBlock, 0, s>>>(push, q, qpre, qlen, fr, vis, nx, touch, mask, probe, own_nx, own_lo,
+                                                  nullptr, nullptr);
+    else ms_push<><<<256 * 8, kBlock, 0, s>>>(push, q, qpre, qlen, fr, vis, nx, touch, mask, probe, own_nx, own_lo,
+                                              nullptr, nullptr);
+    return hipGetLastError();
+}
+hipError_t k_ms_push_sparse(const View& push, const int32_t* q, const int64_t* qpre, int64_t qlen, const uint64_t* fr,
+                            const uint64_t* vis, uint64_t* nx, int32_t* qn, Counters* cnt, hipStream_t s) {
+    if (!vis || !qn || !cnt) return hipErrorInvalidValue;
+    ms_push<4, true><<<256 * 8, kBlock, 0, s>>>(push, q, qpre, qlen, fr, vis, nx, PackTouch{}, ~0ULL, true, nullptr, 0, qn,
+                                               cnt);
+    return hipGetLastError();
+}
+hipError_t k_ms_settle_sparse(const View& push, const int32_t* qn, int64_t* qdeg, uint64_t* vis, const uint64_t* nx,
+                              LevelPlanes lvl, Counters* cnt, int32_t next_level, hipStream_t s,
+                              unsigned long long* srcent, const int32_t* qp, int64_t qplen, uint64_t* fr) {
+    ms_settle_sparse<<<512, kBlock, 0, s>>>(push, qn, qdeg, vis, nx, lvl, cnt, next_level, srcent, qp, qplen, fr);
     return hipGetLastError();
 }
 hipError_t k_ms_push_ranged(const View& push, const int32_t* q, int64_t qlen, int64_t n_active, int64_t S,
