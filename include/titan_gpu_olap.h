@@ -355,9 +355,14 @@ int  tgo_copy_multi_distances(tgo_ctx* ctx, int32_t source, int64_t* dist_out);
  * frontier has at most f x (rows with entries) entries run in the sparse form (the touched
  * vertices are queued by the push and settled from that queue, no pass over every mask);
  * 0 = never; -1 = TGO_MS_SPARSE or the default.  Same distances either way. */
+/* TGO_TUNE_TRI_WAVE_ROW / TGO_TUNE_TRI_BLOCK_ROW (tgo_triangles): the forward-row length from
+ * which a row is intersected by its whole wave / staged in LDS and intersected by a whole
+ * workgroup (rows too long for LDS stay with the wave); an integer >= 1, < 0 = the default.
+ * Same counts for every value (tests use tiny values so that small graphs reach every path). */
 enum { TGO_TUNE_MS_SPLIT = 1, TGO_TUNE_MS_GHOST = 2, TGO_TUNE_DS_BINS = 3, TGO_TUNE_DS_PILE_CAP = 4,
        TGO_TUNE_DS_DONE = 5, TGO_TUNE_MS_COLD = 6, TGO_TUNE_DS_PULL = 7, TGO_TUNE_DS_SMALL = 8,
-       TGO_TUNE_MS_STAY = 9, TGO_TUNE_MS_SPARSE = 10 };
+       TGO_TUNE_MS_STAY = 9, TGO_TUNE_MS_SPARSE = 10, TGO_TUNE_TRI_WAVE_ROW = 11,
+       TGO_TUNE_TRI_BLOCK_ROW = 12 };
 int  tgo_set_tuning(tgo_ctx* ctx, int32_t key, double value);
 
 /* ---- Tracing (the reference's only hook is FulgoraGraphComputer.java:143,307
@@ -401,6 +406,29 @@ typedef struct { int32_t scope; int32_t flags; } tgo_cc_args;
 typedef struct { int64_t components; int32_t rounds; int32_t path; } tgo_cc_info;
 int  tgo_components(tgo_ctx* ctx, const tgo_cc_args* args, int64_t* label_out, tgo_cc_info* info);
 int  tgo_copy_components(tgo_ctx* ctx, int64_t* label_out);
+
+/* ---- Triangle counting and clustering coefficients ------------------------------------
+ * Over the simple undirected projection of a bothE load: u ~ v iff u != v and an OUT or IN entry
+ * of u names v (parallel edges, the two directions of a pair and self-loops collapse).  With
+ * N(v) the neighbour set and d(v) = |N(v)|, per vertex in row order:
+ *   tri[v]  the unordered pairs {a, b} of N(v) with a ~ b
+ *   deg[v]  d(v)
+ *   lcc[v]  (double)(2 tri[v]) / (double)(d(v) (d(v) - 1)), 0.0 when d(v) < 2 (one IEEE division
+ *           of integers below 2^53: bit-exact)
+ * info: triangles = sum(tri) / 3, wedges = sum d (d - 1) / 2, simple_edges = sum(d) / 2,
+ * max_forward = the longest oriented row (neighbours with a smaller internal id).  All counts are
+ * integers: results are bit-identical run to run and for every TGO_TUNE_TRI_* value.  A vertex
+ * cut counts as its canonical vertex; a vertex without entries gets 0 / 0 / 0.0.
+ * args->scope must be TGO_SCOPE_BOTH_E and the loaded scope (else TGO_E_INVALID), args->flags 0.
+ * Lists that are not each other's transpose (tgo_load_csr with asymmetric rows) make the relation
+ * asymmetric: TGO_E_UNSUPPORTED; so does a partitioned ctx.  tri_out NULL: the results stay on the
+ * device (tgo_copy_triangles, whose out-pointers may each be NULL; tgo_result_rows kind
+ * TGO_RESULT_TRIANGLES).  tgo_stats.iterations = 1; the forward lists are built on the first
+ * run of a load and stay cached with it (tgo_stats.device_bytes). */
+typedef struct { int32_t scope; int32_t flags; } tgo_tri_args;
+typedef struct { int64_t triangles, wedges, simple_edges, max_forward; } tgo_tri_info;
+int  tgo_triangles(tgo_ctx* ctx, const tgo_tri_args* args, int64_t* tri_out, tgo_tri_info* info);
+int  tgo_copy_triangles(tgo_ctx* ctx, int64_t* tri_out, int64_t* deg_out, double* lcc_out);
 
 /* ---- Generic vertex programs ----------------------------------------
  * A vertex program the engine does not implement natively runs its execute() on the host
@@ -505,6 +533,9 @@ int  tgo_dense_ids(tgo_ctx* ctx, const int64_t* titan_ids, int64_t count, int64_
  *   DEGREE    OLAPTest.DegreeCounter DEGREE (Integer) on every executed vertex
  *   COMPONENT tgo_components' label (Long; an Integer key when every Titan id of the graph is
  *             in int range, else TGO_E_INVALID) on every executed vertex
+ *   TRIANGLES tgo_triangles' count (key_ids[0]: Long; an Integer key when every count is in int
+ *             range, else TGO_E_INVALID) and clustering coefficient (key_ids[1]: Double) on every
+ *             executed vertex
  * Compute keys are typed property keys of those datatypes, or generic keys (TGO_DT_OBJECT: what
  * getOrCreatePropertyKey makes for a key the program sets without a schema, DefaultSchemaMaker
  * .java:46-48), whose values carry their class (Long 13, Double 20, Integer 12).  Relation ids are
@@ -513,11 +544,11 @@ int  tgo_dense_ids(tgo_ctx* ctx, const int64_t* titan_ids, int64_t count, int64_
  * nrows keys, nrows+1 entry / byte offsets, nbytes bytes and nentries limit|valuePos words
  * (the tgo_rows layout, so the rows can be scanned again). */
 typedef enum { TGO_RESULT_DISTANCE = 0, TGO_RESULT_PAGERANK = 1, TGO_RESULT_DEGREE = 2,
-               TGO_RESULT_VALUES = 3, TGO_RESULT_COMPONENT = 4 } tgo_result_kind;
+               TGO_RESULT_VALUES = 3, TGO_RESULT_COMPONENT = 4, TGO_RESULT_TRIANGLES = 5 } tgo_result_kind;
 typedef struct {
     int32_t kind;                 /* tgo_result_kind                                          */
     int32_t reserved;             /* TGO_RESULT_VALUES: tgo_value_type of the values           */
-    int64_t key_ids[2];           /* [0] DISTANCE / PAGE_RANK / DEGREE / COMPONENT key; [1] OUTGOING_EDGE_COUNT */
+    int64_t key_ids[2];           /* [0] DISTANCE / PAGE_RANK / DEGREE / COMPONENT / TRIANGLES key; [1] OUTGOING_EDGE_COUNT / CLUSTERING */
     int32_t datatypes[2];         /* tgo_datatype of each key                                  */
     int64_t relation_id_base;
 } tgo_result_args;

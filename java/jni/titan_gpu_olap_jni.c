@@ -287,6 +287,21 @@ JNIEXPORT jlongArray JNICALL JFN(components)(JNIEnv* env, jclass cls, jlong h) {
     return distances(env, h, run_components, &a);
 }
 
+/* tgo_triangles over the bothE load: every vertex's triangle count in row order, or NULL on
+ * error (the coefficients follow from the counts and the projection's degrees; write-back
+ * encodes both keys on the device, tgo_result_rows kind TGO_RESULT_TRIANGLES). */
+static int run_triangles(tgo_ctx* c, const void* a, int64_t* o) {
+    return tgo_triangles(c, (const tgo_tri_args*)a, o, NULL);
+}
+
+JNIEXPORT jlongArray JNICALL JFN(triangles)(JNIEnv* env, jclass cls, jlong h) {
+    (void)cls;
+    tgo_tri_args a;
+    memset(&a, 0, sizeof a);
+    a.scope = TGO_SCOPE_BOTH_E;
+    return distances(env, h, run_triangles, &a);
+}
+
 /* tgo_result_rows: Object[5] = {long[] rowKeys, long[] rowEntryBegin, long[] rowByteBegin,
  * long[] entryLimitValuePos, byte[] entryBytes}, or NULL on error (status: lastError; a result
  * beyond the int32 index range of a Java array: IllegalStateException). */

@@ -44,7 +44,8 @@ import java.util.concurrent.Future;
  * Supported: tmain's PageRankVertexProgram, ShortestDistanceVertexProgram and
  * OLAPTest.DegreeCounter (matched by class name; their parameters are read from
  * storeState(), or the DegreeCounter's length field), and a ConnectedComponentVertexProgram
- * (weakly connected components over bothE, tgo_components).
+ * (weakly connected components over bothE, tgo_components) and a TriangleCountVertexProgram
+ * (triangles and clustering coefficients of the simple undirected projection, tgo_triangles).
  *
  * Write-back (FulgoraGraphComputer.java:248-305): with Persist.VERTEX_PROPERTIES the compute
  * keys are encoded on the device (tgo_result_rows: single-cardinality property entries, one
@@ -537,6 +538,8 @@ public class GpuGraphComputer implements TitanGraphComputer {
                     return new DegreeCount(lengthOf(p));
                 case "com.thinkaurelius.titan.olap.ConnectedComponentVertexProgram":
                     return new ConnectedComponent();
+                case "com.thinkaurelius.titan.olap.TriangleCountVertexProgram":
+                    return new TriangleCount();
                 default:
                     throw new TitanException("vertex program " + p.getClass().getName() + " is not supported on the GPU path");
             }
@@ -680,6 +683,31 @@ public class GpuGraphComputer implements TitanGraphComputer {
         void emit(long[] ids, Map<String, Object> values, FulgoraMapEmitter emitter) {
             long[] c = (long[]) values.get(COMPONENT);
             for (int i = 0; i < ids.length; i++) emitter.emit(ids[i], c[i]);
+        }
+    }
+
+    /**
+     * Triangle counting over bothE on the simple undirected projection (tgo_triangles):
+     * TRIANGLES = the pairs of the vertex's neighbours that are neighbours of each other,
+     * CLUSTERING = its local clustering coefficient.  The native call returns the counts; the
+     * write-back encodes both keys on the device (RESULT_TRIANGLES).  One device pass.
+     */
+    static final class TriangleCount extends DeviceProgram {
+        static final String TRIANGLES = "titan.triangleCount.triangles";
+        static final String CLUSTERING = "titan.triangleCount.clusteringCoefficient";
+        int scope() { return TgoNative.SCOPE_BOTH_E; }
+        int iterations() { return 1; }
+        int resultKind() { return TgoNative.RESULT_TRIANGLES; }
+        String[] computeKeys() { return new String[]{TRIANGLES, CLUSTERING}; }
+        int[] computeKeyTypes() { return new int[]{TgoNative.DT_LONG, TgoNative.DT_DOUBLE}; }
+        Map<String, Object> run(long ctx) {
+            Map<String, Object> v = new HashMap<>();
+            v.put(TRIANGLES, TgoNative.checked(ctx, TgoNative.triangles(ctx)));
+            return v;
+        }
+        void emit(long[] ids, Map<String, Object> values, FulgoraMapEmitter emitter) {
+            long[] t = (long[]) values.get(TRIANGLES);
+            for (int i = 0; i < ids.length; i++) emitter.emit(ids[i], t[i]);
         }
     }
 }

@@ -82,11 +82,19 @@ public final class TgoNative {
      */
     public static native long[] components(long ctx);
 
+    /**
+     * tgo_triangles over a bothE load: every vertex's triangle count on the simple undirected
+     * projection, in row order; null on failure.  The clustering coefficients stay on the device
+     * for resultRows (RESULT_TRIANGLES writes both keys).
+     */
+    public static native long[] triangles(long ctx);
+
     /** tgo_stats_get: {ghostVertices, truncatedResults, skippedRows, iterations, loadMs, lastKernelMs}. */
     public static native double[] stats(long ctx);
 
     /** tgo_result_kind */
-    public static final int RESULT_DISTANCE = 0, RESULT_PAGERANK = 1, RESULT_DEGREE = 2, RESULT_COMPONENT = 4;
+    public static final int RESULT_DISTANCE = 0, RESULT_PAGERANK = 1, RESULT_DEGREE = 2, RESULT_COMPONENT = 4,
+            RESULT_TRIANGLES = 5;
     /**
      * tgo_result_rows: the edgestore entries (single-cardinality property entries) of the last
      * program's compute keys, as {long[] rowKeys, long[] rowEntryBegin, long[] rowByteBegin,

@@ -9,7 +9,8 @@ from .computer import (  # noqa: F401
     ClusterCountMapReduce, ClusterPopulationMapReduce, ConnectedComponentVertexProgram,
     DegreeCounter, DegreeMapper, ExecutionException, GpuGraph, GpuGraphComputer, KeyValue,
     PageRankMapReduce, PageRankVertexProgram, ShortestDistanceMapReduce,
-    ShortestDistanceVertexProgram, TitanGraphComputer,
+    ShortestDistanceVertexProgram, TitanGraphComputer, TransitivityMapReduce, TriangleCountMapReduce,
+    TriangleCountVertexProgram,
 )
 from .generic import (  # noqa: F401
     ComputeKeyMapReduce, EdgeExpr, FulgoraMemory, GenericVertexProgram, MessageScope, Messenger, Vertices,
@@ -24,4 +25,5 @@ __all__ = [
     "TitanGraphComputer", "ComputeKeyMapReduce", "FulgoraMemory", "GenericVertexProgram", "MessageScope",
     "Messenger", "Vertices", "EdgeExpr", "TraversalVertexProgram",
     "ConnectedComponentVertexProgram", "ClusterPopulationMapReduce", "ClusterCountMapReduce",
+    "TriangleCountVertexProgram", "TriangleCountMapReduce", "TransitivityMapReduce",
 ]

@@ -377,6 +377,30 @@ class ConnectedComponentVertexProgram(VertexProgram):
         return ConnectedComponentVertexProgram.Builder()
 
 
+class TriangleCountVertexProgram(VertexProgram):
+    """Triangle counting over bothE on the simple undirected projection (tgo_triangles): parallel
+    edges, the two directions of a pair and self-loops collapse.  TRIANGLES = the pairs of the
+    vertex's neighbours that are neighbours of each other (Long), CLUSTERING = its local
+    clustering coefficient 2 T / (d (d - 1)) (Double, 0.0 below two neighbours).  Both are compute
+    keys and are written back; the projection's degree d rides along as a third vertex property,
+    DEGREE, which is NOT a compute key (never persisted): TransitivityMapReduce needs it.  One
+    device pass: memory.getIteration() is 1.  Result graph and persist preference as
+    ShortestDistanceVertexProgram."""
+    TRIANGLES = "titan.triangleCount.triangles"
+    CLUSTERING = "titan.triangleCount.clusteringCoefficient"
+    DEGREE = "titan.triangleCount.degree"
+    compute_keys = (TRIANGLES, CLUSTERING)
+    scope_name = "bothE"
+
+    class Builder:
+        def create(self, graph=None):
+            return TriangleCountVertexProgram()
+
+    @staticmethod
+    def build():
+        return TriangleCountVertexProgram.Builder()
+
+
 # ----------------------------------------------------------------------------- map-reduces
 class MapReduce:
     memory_key = ""
@@ -484,6 +508,45 @@ class ClusterCountMapReduce(MapReduce):
     def emit(self, ids, props):
         lab = props.get(ConnectedComponentVertexProgram.COMPONENT)
         return 0 if lab is None else int(len(np.unique(np.asarray(lab, dtype=np.int64))))
+
+
+class TriangleCountMapReduce(MapReduce):
+    """The graph's triangles: every triangle is counted at its three corners, so sum // 3."""
+    DEFAULT_MEMORY_KEY = "triangleCount"
+
+    def __init__(self, key=DEFAULT_MEMORY_KEY):
+        self.memory_key = key
+
+    @staticmethod
+    def build():
+        return _MemoryKeyBuilder(TriangleCountMapReduce)
+
+    def emit(self, ids, props):
+        tri = props.get(TriangleCountVertexProgram.TRIANGLES)
+        return 0 if tri is None else sum(int(t) for t in np.asarray(tri, dtype=np.int64)) // 3
+
+
+class TransitivityMapReduce(MapReduce):
+    """Global clustering coefficient 3 T / W: T the triangles, W = sum d (d - 1) / 2 the wedges,
+    from the program's TRIANGLES and (non-persisted) DEGREE properties, in exact integers up to the
+    one division; 0.0 for a graph without a wedge."""
+    DEFAULT_MEMORY_KEY = "transitivity"
+
+    def __init__(self, key=DEFAULT_MEMORY_KEY):
+        self.memory_key = key
+
+    @staticmethod
+    def build():
+        return _MemoryKeyBuilder(TransitivityMapReduce)
+
+    def emit(self, ids, props):
+        tri = props.get(TriangleCountVertexProgram.TRIANGLES)
+        deg = props.get(TriangleCountVertexProgram.DEGREE)
+        if tri is None or deg is None:
+            return 0.0
+        t = sum(int(x) for x in np.asarray(tri, dtype=np.int64)) // 3
+        w = sum(int(d) * (int(d) - 1) // 2 for d in np.asarray(deg, dtype=np.int64))
+        return 3 * t / w if w else 0.0
 
 
 class DegreeMapper(MapReduce):
@@ -608,7 +671,9 @@ class GpuGraphComputer(TitanGraphComputer):
                     PageRankVertexProgram: (L.RESULT_PAGERANK, (PageRankVertexProgram.PAGE_RANK,
                                                                 PageRankVertexProgram.OUTGOING_EDGE_COUNT)),
                     DegreeCounter: (L.RESULT_DEGREE, (DegreeCounter.DEGREE,)),
-                    ConnectedComponentVertexProgram: (L.RESULT_COMPONENT, (ConnectedComponentVertexProgram.COMPONENT,))}
+                    ConnectedComponentVertexProgram: (L.RESULT_COMPONENT, (ConnectedComponentVertexProgram.COMPONENT,)),
+                    TriangleCountVertexProgram: (L.RESULT_TRIANGLES, (TriangleCountVertexProgram.TRIANGLES,
+                                                                      TriangleCountVertexProgram.CLUSTERING))}
 
     def _result_mode(self):
         """resultMode if set, else the program's preferred (ResultGraph, Persist) as Fulgora
@@ -701,6 +766,15 @@ class GpuGraphComputer(TitanGraphComputer):
             eng = self.graph.engine_for(L.SCOPE_BOTH_E)
             props[ConnectedComponentVertexProgram.COMPONENT], info = eng.components()
             iteration = info["rounds"]
+            ids = eng.vertex_ids()
+        elif isinstance(p, TriangleCountVertexProgram):
+            eng = self.graph.engine_for(L.SCOPE_BOTH_E)
+            eng.triangles(fetch=False)
+            tri, deg, lcc = eng.copy_triangles()
+            props[TriangleCountVertexProgram.TRIANGLES] = tri
+            props[TriangleCountVertexProgram.CLUSTERING] = lcc
+            props[TriangleCountVertexProgram.DEGREE] = deg        # for TransitivityMapReduce; not a compute key
+            iteration = 1
             ids = eng.vertex_ids()
         else:
             raise TitanException(L.TGO_E_UNSUPPORTED, f"vertex program {type(p).__name__} is not supported on the GPU path")

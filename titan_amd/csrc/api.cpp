@@ -91,6 +91,9 @@ struct tgo_ctx {
                                 // hot head (and segment); < 0: TGO_MS_COLD / on
     double ms_stay = -1.0;      // tgo_set_tuning(TGO_TUNE_MS_STAY): gamma; < 0: TGO_MS_STAY / the default
     double ms_sparse = -1.0;    // tgo_set_tuning(TGO_TUNE_MS_SPARSE): fraction of n_active; < 0: TGO_MS_SPARSE / the default
+    int64_t tri_wave_row = -1;  // tgo_set_tuning(TGO_TUNE_TRI_WAVE_ROW / _BLOCK_ROW): forward-row lengths from
+    int64_t tri_block_row = -1; // which a wave / a workgroup takes the row; < 0: the defaults (kTriWaveRow / kTriBlockRow)
+    int64_t tri_max = 0;        // largest count of the last tgo_triangles (an Integer key's range check)
     // state a native partitioned driver keeps between runs on this graph (part_driver.cpp:
     // the PageRank ghost lists); dropped with the graph
     std::shared_ptr<void> part_state;
@@ -1336,6 +1339,13 @@ int tgo_set_tuning(tgo_ctx* ctx, int32_t key, double value) {
         if (!(value >= 0.0) || value > 9.0e15) return fail(ctx, TGO_E_INVALID, "TGO_TUNE_DS_PILE_CAP: entries >= 0");
         ctx->ds_pile_cap = static_cast<int64_t>(value);
         return TGO_OK;
+    case TGO_TUNE_TRI_WAVE_ROW:
+    case TGO_TUNE_TRI_BLOCK_ROW: {
+        if (!(value < 0.0) && !(value >= 1.0 && value <= 9.0e15 && value == static_cast<double>(static_cast<int64_t>(value))))
+            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_TRI_WAVE_ROW / _BLOCK_ROW: a row length >= 1 (< 0: the default)");
+        (key == TGO_TUNE_TRI_WAVE_ROW ? ctx->tri_wave_row : ctx->tri_block_row) = value < 0.0 ? -1 : static_cast<int64_t>(value);
+        return TGO_OK;
+    }
     default:
         return fail(ctx, TGO_E_INVALID, "tgo_set_tuning: unknown key");
     }
@@ -2173,6 +2183,117 @@ int tgo_copy_components(tgo_ctx* ctx, int64_t* label_out) {
     return TGO_OK;
 }
 
+// ------------------------------------------------------------------ triangles
+// Triangle counting (tri.hip).  The forward lists, the degrees and the totals' words live with the
+// graph (dev_alloc: released with it); per run: counts in internal order = sc.dist, coefficients =
+// sc.vec[0], the block and wave kernels' row queues = sc.level and sc.q[0], row-order staging = sc.msg.
+// Defaults of TGO_TUNE_TRI_WAVE_ROW / _BLOCK_ROW (DESIGN.md 4.5 has the sweep).
+constexpr int64_t kTriWaveRow = 8, kTriBlockRow = 8;
+
+static int tri_forward_lists(tgo_ctx* ctx) {
+    DevGraph& g = ctx->g;
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    const int64_t n = g.n;
+    DevSpan span(st, "triangles.forward_lists");
+    HIP_TRY(dev_alloc(ctx, g.tri_tot, 16));
+    HIP_TRY(dev_alloc(ctx, g.tri_deg, n));
+    HIP_TRY(dev_alloc(ctx, g.tri_foff, n + 1));
+    HIP_TRY(hipMemsetAsync(g.tri_tot, 0, 16 * sizeof(unsigned long long), st));
+    // count, scan, fill: |fwd(v)| in sc.qdeg (n + 2)
+    HIP_TRY(k_tri_fwd_count(g.out, g.in, n, s.qdeg, g.tri_deg, &g.tri_tot[0], st));
+    HIP_TRY(scan_exclusive_i64(s.cub_tmp, s.cub_bytes, s.qdeg, g.tri_foff, n + 1, st));
+    int64_t fnnz = 0;
+    unsigned long long longest = 0;
+    HIP_TRY(hipMemcpyAsync(&fnnz, g.tri_foff + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&longest, g.tri_tot, sizeof(longest), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (fnnz < 0 || fnnz > g.out.nnz + g.in.nnz) return fail(ctx, TGO_E_HIP, "forward lists: inconsistent entry count");
+    HIP_TRY(dev_alloc(ctx, g.tri_fadj, fnnz));
+    HIP_TRY(k_tri_fwd_fill(g.out, g.in, n, g.tri_foff, g.tri_fadj, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    g.tri_fnnz = fnnz;
+    g.tri_max_fwd = static_cast<int64_t>(longest);
+    ctx->st.device_bytes = ctx->dev_bytes;
+    return TGO_OK;
+}
+
+static int tri_copy_out(tgo_ctx* ctx, const int64_t* internal, void* out) {
+    HIP_TRY(k_unpermute_i64(internal, ctx->g.perm, ctx->sc.msg, ctx->g.n, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out, ctx->sc.msg, ctx->g.n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return TGO_OK;
+}
+
+int tgo_triangles(tgo_ctx* ctx, const tgo_tri_args* a, int64_t* tri_out, tgo_tri_info* info) {
+    if (!ctx) return TGO_E_INVALID;
+    ctx->res_kind = -1;
+    if (!a) return fail(ctx, TGO_E_INVALID, "null args");
+    int rc = check_program(ctx, a->scope);
+    if (rc) return rc;
+    if (a->scope != TGO_SCOPE_BOTH_E)
+        return fail(ctx, TGO_E_INVALID, "triangles are counted over bothE; load the graph with TGO_SCOPE_BOTH_E");
+    if (a->flags != 0) return fail(ctx, TGO_E_INVALID, "tgo_tri_args.flags must be 0");
+    if (ctx->g.partitioned) return fail(ctx, TGO_E_UNSUPPORTED, "triangles are counted on a one-GPU load");
+    if (ctx->g.has_transpose)
+        return fail(ctx, TGO_E_UNSUPPORTED,
+                    "the loaded OUT and IN lists are not each other's transpose (tgo_load_csr with asymmetric rows): "
+                    "the neighbour relation is asymmetric, triangles are not defined on it");
+    (void)hipSetDevice(ctx->opts.device);
+    DevGraph& g = ctx->g;
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    const int64_t n = g.n;
+    if (!g.tri_fadj && (rc = tri_forward_lists(ctx))) return rc;
+    int64_t* const tri = s.dist;
+    double* const lcc = s.vec[0];
+    HIP_TRY(hipEventRecord(ctx->ev0, st));
+    HIP_TRY(k_fill_i64(tri, 0, n, st));
+    HIP_TRY(hipMemsetAsync(g.tri_tot + 1, 0, 15 * sizeof(unsigned long long), st));
+    {
+        DevSpan span(st, "triangles.count", {"forward_entries", g.tri_fnnz}, {"max_forward", g.tri_max_fwd});
+        HIP_TRY(k_tri_count(g.tri_foff, g.tri_fadj, n, ctx->tri_wave_row < 0 ? kTriWaveRow : ctx->tri_wave_row,
+                            ctx->tri_block_row < 0 ? kTriBlockRow : ctx->tri_block_row, g.tri_max_fwd, tri, s.level,
+                            s.q[0], &g.tri_tot[5], st));
+    }
+    {
+        DevSpan span(st, "triangles.finish");
+        HIP_TRY(k_tri_finish(tri, g.tri_deg, n, lcc, g.tri_tot + 1, st));
+    }
+    unsigned long long tot[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(tot, g.tri_tot + 1, sizeof tot, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(ctx->ev1, st));
+    HIP_TRY(hipEventSynchronize(ctx->ev1));
+    trace_resolve(st);
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    ctx->st.last_kernel_ms = ms;
+    ctx->st.iterations = 1;
+    ctx->tri_max = static_cast<int64_t>(tot[3]);
+    if (info)
+        *info = tgo_tri_info{static_cast<int64_t>(tot[0] / 3), static_cast<int64_t>(tot[1]),
+                             static_cast<int64_t>(tot[2] / 2), g.tri_max_fwd};
+    if (tri_out && (rc = tri_copy_out(ctx, tri, tri_out))) return rc;
+    ctx->res_kind = TGO_RESULT_TRIANGLES;
+    ctx->res_empty = false;
+    ctx->res_src = ResultSource{tri, lcc};
+    return TGO_OK;
+}
+
+int tgo_copy_triangles(tgo_ctx* ctx, int64_t* tri_out, int64_t* deg_out, double* lcc_out) {
+    if (!ctx) return TGO_E_INVALID;
+    if (!ctx->loaded) return fail(ctx, TGO_E_STATE, "no graph loaded");
+    if (ctx->res_kind != TGO_RESULT_TRIANGLES)
+        return fail(ctx, TGO_E_STATE, "tgo_triangles is not the last program run on this ctx");
+    (void)hipSetDevice(ctx->opts.device);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    int rc = TGO_OK;
+    if (tri_out && (rc = tri_copy_out(ctx, ctx->sc.dist, tri_out))) return rc;
+    if (deg_out && (rc = tri_copy_out(ctx, ctx->g.tri_deg, deg_out))) return rc;
+    if (lcc_out && (rc = tri_copy_out(ctx, reinterpret_cast<const int64_t*>(ctx->sc.vec[0]), lcc_out))) return rc;
+    return TGO_OK;
+}
+
 int tgo_pagerank(tgo_ctx* ctx, const tgo_pr_args* a, double* pr_out) {
     if (!ctx) return TGO_E_INVALID;
     ctx->res_kind = -1;
@@ -2349,7 +2470,7 @@ static int result_rows_impl(tgo_ctx* ctx, const tgo_result_args* a, const Result
 int tgo_result_rows(tgo_ctx* ctx, const tgo_result_args* a, tgo_result_size* size, const tgo_rows_buf* out) {
     if (!ctx) return TGO_E_INVALID;
     if (!a || !size) return fail(ctx, TGO_E_INVALID, "null args");
-    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_COMPONENT || a->kind == TGO_RESULT_VALUES)
+    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_TRIANGLES || a->kind == TGO_RESULT_VALUES)
         return fail(ctx, TGO_E_INVALID, "invalid result kind");
     if (ctx->res_kind != a->kind)
         return fail(ctx, TGO_E_STATE, "no finished program of that kind is the last one run on this ctx");
@@ -2358,6 +2479,8 @@ int tgo_result_rows(tgo_ctx* ctx, const tgo_result_args* a, tgo_result_size* siz
         for (const int64_t id : ctx->titan_id)
             if (id < INT32_MIN || id > INT32_MAX)
                 return fail(ctx, TGO_E_INVALID, "a value of an Integer compute key is out of int range");
+    if (a->kind == TGO_RESULT_TRIANGLES && a->datatypes[0] == TGO_DT_INTEGER && ctx->tri_max > INT32_MAX)
+        return fail(ctx, TGO_E_INVALID, "a value of an Integer compute key is out of int range");
     return result_rows_impl(ctx, a, ctx->res_src, ctx->res_empty, size, out);
 }
 

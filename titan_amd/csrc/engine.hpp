@@ -467,6 +467,14 @@ struct DevGraph {
     int32_t msc_scope = -1;         // scope the layout was built for (-1: none yet)
     int64_t msc_req = 0;            // and its hot head
     int64_t* cc_tid = nullptr;      // n: Titan id of every internal index (tgo_components, built on its first run)
+    // forward lists of the simple undirected projection (tgo_triangles, built on its first run):
+    // fwd(v) = the sorted distinct neighbours u < v, internal ids
+    int64_t* tri_foff = nullptr;    // n + 1
+    int32_t* tri_fadj = nullptr;    // tri_fnnz
+    int64_t* tri_deg = nullptr;     // n: d(v) = distinct neighbours other than v
+    unsigned long long* tri_tot = nullptr;   // 16 words: [0] longest forward row; per run: [1] sum tri,
+                                    // [2] wedges, [3] sum d, [4] max tri, [5..8] the row queues' counts and tickets
+    int64_t tri_fnnz = 0, tri_max_fwd = 0;
 };
 
 // Multi-source BFS levels as bit planes: the level of (v, source r) is
@@ -869,6 +877,24 @@ hipError_t k_cc_label(const int32_t* parent, const int64_t* minid, int64_t n, in
 // label); *roots += vertices whose label is their own id (= distinct labels at the fixed point)
 hipError_t k_cc_pull_round(const View& pull, int64_t n, int64_t* label, unsigned long long* changed, hipStream_t s);
 hipError_t k_cc_count_own(const int64_t* label, const int64_t* tid, int64_t n, unsigned long long* roots, hipStream_t s);
+
+// Triangle counting (tri.hip).  Forward lists: k_tri_fwd_count writes |fwd(v)| to fcnt (n + 1,
+// fcnt[n] = 0), d(v) to deg and raises *max_fwd to the longest forward row; k_tri_fwd_fill writes
+// the rows at their scanned offsets.  k_tri_count adds every triangle to tri (n, zero before) at its
+// three corners: rows of >= wave_row forward entries by their wave, rows of >= block_row entries
+// (at most kTriLdsEntries) by a workgroup from LDS, through the queues wlist / blist (n each) and
+// q (4 words, zero before: block rows, wave rows and the two kernels' tickets).
+// k_tri_finish: lcc, and tot[0..3] += sum tri, wedges, sum d, max tri.
+constexpr int64_t kTriLdsEntries = 16384;    // entries + their counters: 128 KB of the CU's 160 KB LDS
+hipError_t k_tri_fwd_count(const DevCsr& out, const DevCsr& in, int64_t n, int64_t* fcnt, int64_t* deg,
+                           unsigned long long* max_fwd, hipStream_t s);
+hipError_t k_tri_fwd_fill(const DevCsr& out, const DevCsr& in, int64_t n, const int64_t* foff, int32_t* fadj,
+                          hipStream_t s);
+hipError_t k_tri_count(const int64_t* foff, const int32_t* fadj, int64_t n, int64_t wave_row, int64_t block_row,
+                       int64_t max_fwd, int64_t* tri, int32_t* blist, int32_t* wlist, unsigned long long* q,
+                       hipStream_t s);
+hipError_t k_tri_finish(const int64_t* tri, const int64_t* deg, int64_t n, double* lcc, unsigned long long* tot,
+                        hipStream_t s);
 
 // PageRank gather diagnostics: [diag_lo, diag_hi) = only sources in this range are gathered
 // (the others read as 0; results invalid) — attributes the update's time to source ranges.

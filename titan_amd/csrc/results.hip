@@ -51,12 +51,13 @@ struct ResArgs {
     uint8_t lead[2];        // first value byte: 0x00 = the null flag of a typed key; a generic key's
                             // class registration (writePositive(13 / 20 / 12) = 0x8D / 0x94 / 0x8C)
     int64_t rel_base;
-    // how a value is written, decided once on the host from kind / vdt (the kernels branch on
-    // these two words only): varint = an Integer encoding (DEGREE, or an Integer key of a generic
-    // program / the component labels); flip = the sign-bit flip of a Long encoding
-    // (LongSerializer: v - Long.MIN_VALUE), 0 for the raw IEEE bits of a Double
-    int varint;
-    uint64_t flip;
+    // how a value is written, decided once on the host from kind / vdt, per column position (the
+    // kernels branch on these two words only): varint = an Integer encoding (DEGREE, or an Integer
+    // key of a generic program / the component labels / the triangle counts); flip = the sign-bit
+    // flip of a Long encoding (LongSerializer: v - Long.MIN_VALUE), 0 for the raw IEEE bits of a
+    // Double
+    int varint[2];
+    uint64_t flip[2];
 };
 
 // Value of slot `k` for internal vertex v; false when the vertex holds no such property.
@@ -66,9 +67,10 @@ __device__ inline bool value_of(const ResArgs& a, const void* v0, const void* v1
         bits = static_cast<uint64_t>(d);
         return d != TGO_DIST_ABSENT;
     }
-    if (a.kind == TGO_RESULT_PAGERANK) {
-        const double x = static_cast<const double*>(k == 0 ? v0 : v1)[v];
-        bits = static_cast<uint64_t>(__double_as_longlong(x));
+    if (a.kind == TGO_RESULT_PAGERANK || a.kind == TGO_RESULT_TRIANGLES) {
+        // two 8-byte values on every executed vertex: the ranks and edge counts (doubles), or the
+        // triangle counts (int64) and clustering coefficients (doubles) — raw bits either way
+        bits = static_cast<const uint64_t*>(k == 0 ? v0 : v1)[v];
         return true;
     }
     if (a.kind == TGO_RESULT_COMPONENT) {       // a label on every executed vertex
@@ -83,8 +85,8 @@ __device__ inline bool value_of(const ResArgs& a, const void* v0, const void* v1
     return true;
 }
 
-__device__ inline int value_len(const ResArgs& a, uint64_t bits) {
-    if (a.varint) return 1 + pos_len(zigzag(static_cast<int64_t>(bits)));
+__device__ inline int value_len(const ResArgs& a, int j, uint64_t bits) {
+    if (a.varint[j]) return 1 + pos_len(zigzag(static_cast<int64_t>(bits)));
     return 9;
 }
 
@@ -109,7 +111,7 @@ __global__ void res_size(ResArgs a, const int32_t* perm, const void* v0, const v
     for (int64_t j = 0; j < ne; ++j) {
         uint64_t bits;
         value_of(a, v0, v1, perm[r], a.slot[j], bits);
-        bytes += a.hlen[j] + value_len(a, bits) + pos_len(static_cast<uint64_t>(a.rel_base + e0 + j));
+        bytes += a.hlen[j] + value_len(a, static_cast<int>(j), bits) + pos_len(static_cast<uint64_t>(a.rel_base + e0 + j));
     }
     bcnt[r] = bytes;
 }
@@ -135,10 +137,10 @@ __global__ void res_write(ResArgs a, const int32_t* perm, const void* v0, const 
         for (int i = 0; i < a.hlen[j]; ++i) *p++ = a.hdr[j][i];
         const int64_t vpos = p - ent;
         *p++ = a.lead[j];                              // null flag (typed key) or value class (generic key)
-        if (a.varint) {
+        if (a.varint[j]) {
             p = put_pos(p, zigzag(static_cast<int64_t>(bits)));
         } else {
-            const uint64_t be = bits ^ a.flip;
+            const uint64_t be = bits ^ a.flip[j];
             for (int i = 7; i >= 0; --i) *p++ = static_cast<uint8_t>(be >> (8 * i));
         }
         p = put_pos(p, static_cast<uint64_t>(a.rel_base + e0 + j));
@@ -181,17 +183,20 @@ int encode_results(const ResultSource& src, const tgo_result_args* a, const int3
                    std::string& err) {
     ResArgs ra{};
     ra.kind = a->kind;
-    ra.nkeys = a->kind == TGO_RESULT_PAGERANK ? 2 : 1;
+    ra.nkeys = a->kind == TGO_RESULT_PAGERANK || a->kind == TGO_RESULT_TRIANGLES ? 2 : 1;
     ra.rel_base = a->relation_id_base;
-    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_COMPONENT) { err = "unknown result kind"; return TGO_E_INVALID; }
-    int want[5][2] = {{TGO_DT_LONG, 0}, {TGO_DT_DOUBLE, TGO_DT_DOUBLE}, {TGO_DT_INTEGER, 0}, {0, 0}, {TGO_DT_LONG, 0}};
+    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_TRIANGLES) { err = "unknown result kind"; return TGO_E_INVALID; }
+    int want[6][2] = {{TGO_DT_LONG, 0}, {TGO_DT_DOUBLE, TGO_DT_DOUBLE}, {TGO_DT_INTEGER, 0}, {0, 0}, {TGO_DT_LONG, 0},
+                      {TGO_DT_LONG, TGO_DT_DOUBLE}};
     // StandardSerializer registration numbers of the value classes (:71-81): Long 13, Double 20, Integer 12
-    uint8_t reg[5] = {0x80 | 13, 0x80 | 20, 0x80 | 12, 0, 0x80 | 13};
-    if (a->kind == TGO_RESULT_COMPONENT) {
-        // the labels are longs: a Long key, an Integer key (the caller checked the range) or a
-        // generic key holding Longs — the int64 encoder of a generic program's values
+    // (per key where a kind's two keys differ: the triangle count is a Long, its coefficient a Double)
+    uint8_t reg[6][2] = {{0x80 | 13, 0}, {0x80 | 20, 0x80 | 20}, {0x80 | 12, 0}, {0, 0}, {0x80 | 13, 0},
+                         {0x80 | 13, 0x80 | 20}};
+    if (a->kind == TGO_RESULT_COMPONENT || a->kind == TGO_RESULT_TRIANGLES) {
+        // the labels / counts are longs: a Long key, an Integer key (the caller checked the range)
+        // or a generic key holding Longs — the int64 encoder of a generic program's values
         ra.vdt = a->datatypes[0] == TGO_DT_INTEGER ? TGO_DT_INTEGER : TGO_DT_LONG;
-        want[4][0] = ra.vdt;
+        want[a->kind][0] = ra.vdt;
     }
     if (a->kind == TGO_RESULT_VALUES) {
         // a generic program's key: int64 values as a Long or Integer key (generic: Long),
@@ -200,31 +205,33 @@ int encode_results(const ResultSource& src, const tgo_result_args* a, const int3
         if (ra.vtype == TGO_VAL_INT64) {
             ra.vdt = a->datatypes[0] == TGO_DT_INTEGER ? TGO_DT_INTEGER : TGO_DT_LONG;
             want[3][0] = a->datatypes[0] == TGO_DT_INTEGER ? TGO_DT_INTEGER : TGO_DT_LONG;
-            reg[3] = 0x80 | 13;
+            reg[3][0] = 0x80 | 13;
         } else if (ra.vtype == TGO_VAL_FP64) {
             ra.vdt = TGO_DT_DOUBLE;
             want[3][0] = TGO_DT_DOUBLE;
-            reg[3] = 0x80 | 20;
+            reg[3][0] = 0x80 | 20;
         } else {
             err = "TGO_RESULT_VALUES needs a value type (args.reserved)";
             return TGO_E_INVALID;
         }
     }
-    const bool multi_dt = a->kind == TGO_RESULT_VALUES || a->kind == TGO_RESULT_COMPONENT;
-    ra.varint = a->kind == TGO_RESULT_DEGREE || (multi_dt && ra.vdt == TGO_DT_INTEGER);
-    ra.flip = a->kind == TGO_RESULT_DISTANCE || (multi_dt && ra.vdt == TGO_DT_LONG) ? 0x8000000000000000ULL : 0;
+    const bool multi_dt = a->kind == TGO_RESULT_VALUES || a->kind == TGO_RESULT_COMPONENT || a->kind == TGO_RESULT_TRIANGLES;
+    // by key here, by column position below; the second key of a kind is always a Double
+    const int key_varint[2] = {a->kind == TGO_RESULT_DEGREE || (multi_dt && ra.vdt == TGO_DT_INTEGER), 0};
+    const uint64_t key_flip[2] = {
+        a->kind == TGO_RESULT_DISTANCE || (multi_dt && ra.vdt == TGO_DT_LONG) ? 0x8000000000000000ULL : 0, 0};
     uint8_t lead[2] = {0, 0};
     for (int k = 0; k < ra.nkeys; ++k) {
         if ((a->key_ids[k] & 63) != 5 || (a->key_ids[k] >> 6) <= 0) { err = "compute key is not a user property key id"; return TGO_E_INVALID; }
         if (a->datatypes[k] == TGO_DT_OBJECT) {
-            lead[k] = reg[a->kind];                     // generic key: writeClassAndObject
+            lead[k] = reg[a->kind][k];                     // generic key: writeClassAndObject
         } else if (a->datatypes[k] != want[a->kind][k]) {
-            err = "compute key datatype must be Long (distance), Double (pageRank, edgeCount), Integer (degree), "
-                  "Long or Integer (component) or generic (Object)";
+            err = "compute key datatype must be Long (distance), Double (pageRank, edgeCount, clustering coefficient), "
+                  "Integer (degree), Long or Integer (component, triangles) or generic (Object)";
             return TGO_E_UNSUPPORTED;
         }
     }
-    if (ra.nkeys == 2 && a->key_ids[0] == a->key_ids[1]) { err = "pageRank and edgeCount keys must differ"; return TGO_E_INVALID; }
+    if (ra.nkeys == 2 && a->key_ids[0] == a->key_ids[1]) { err = "the two compute keys must differ"; return TGO_E_INVALID; }
     if (a->relation_id_base <= 0) { err = "relation_id_base must be positive"; return TGO_E_INVALID; }
     // column order = byte order of the headers
     uint8_t h[2][12];
@@ -240,6 +247,8 @@ int encode_results(const ResultSource& src, const tgo_result_args* a, const int3
         ra.hlen[j] = hl[order[j]];
         ra.slot[j] = order[j];
         ra.lead[j] = lead[order[j]];
+        ra.varint[j] = key_varint[order[j]];
+        ra.flip[j] = key_flip[order[j]];
     }
     // scratch: A = row flags, B = their scan (output row index), C = entries per row then
     // byte sizes, D = entry scan; byte scan into A (free once B holds the row scan)

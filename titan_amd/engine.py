@@ -347,6 +347,30 @@ class Engine:
         _check(self.lib, self.ctx, self.lib.tgo_copy_components(self.ctx, L.ptr(out, C.c_int64)))
         return out
 
+    def triangles(self, fetch=True):
+        """Triangle counts of a bothE load over its simple undirected projection (tgo_triangles):
+        (tri, info) — tri[v] = the pairs of v's neighbours that are neighbours of each other, in
+        row order (None when fetch is False: the results stay on the device for copy_triangles /
+        result_rows); info = dict(triangles, wedges, simple_edges, max_forward, transitivity) with
+        transitivity = 3 * triangles / wedges (0.0 without a wedge)."""
+        a = L.TriArgs(L.SCOPE_BOTH_E, 0)
+        info = L.TriInfo()
+        out = np.zeros(self.n, dtype=np.int64) if fetch else None
+        _check(self.lib, self.ctx, self.lib.tgo_triangles(self.ctx, C.byref(a), L.ptr(out, C.c_int64), C.byref(info)))
+        t, w = int(info.triangles), int(info.wedges)
+        return out, {"triangles": t, "wedges": w, "simple_edges": int(info.simple_edges),
+                     "max_forward": int(info.max_forward), "transitivity": 3 * t / w if w else 0.0}
+
+    def copy_triangles(self):
+        """(tri, deg, lcc) of the last triangles() run, in row order: the counts, the degrees of
+        the simple projection (int64) and the local clustering coefficients (float64)."""
+        tri = np.zeros(self.n, dtype=np.int64)
+        deg = np.zeros(self.n, dtype=np.int64)
+        lcc = np.zeros(self.n, dtype=np.float64)
+        _check(self.lib, self.ctx, self.lib.tgo_copy_triangles(self.ctx, L.ptr(tri, C.c_int64), L.ptr(deg, C.c_int64),
+                                                               L.ptr(lcc, C.c_double)))
+        return tri, deg, lcc
+
     def result_rows(self, kind, key_ids, datatypes, relation_id_base):
         """Edgestore entries of the last program's compute keys (tgo_result_rows): the rows
         ResultMode PERSIST writes back (FulgoraGraphComputer.java:248-305)."""
