@@ -355,6 +355,10 @@ int  tgo_copy_multi_distances(tgo_ctx* ctx, int32_t source, int64_t* dist_out);
  * frontier has at most f x (rows with entries) entries run in the sparse form (the touched
  * vertices are queued by the push and settled from that queue, no pass over every mask);
  * 0 = never; -1 = TGO_MS_SPARSE or the default.  Same distances either way. */
+/* TGO_TUNE_MS_HEAD (tgo_bfs_multi): H >= 0 = in a pull level a vertex whose lists hold more
+ * entries than one wave (64) first probes the first H entries of its own lists, every such vertex
+ * of a wave at once, before the whole wave walks what is left of a list the probe did not cover;
+ * a whole number of entries, 0 = off; -1 = TGO_MS_HEAD or the default.  Same distances either way. */
 /* TGO_TUNE_TRI_WAVE_ROW / TGO_TUNE_TRI_BLOCK_ROW (tgo_triangles): the forward-row length from
  * which a row is intersected by its whole wave / staged in LDS and intersected by a whole
  * workgroup (rows too long for LDS stay with the wave); an integer >= 1, < 0 = the default.
@@ -362,7 +366,7 @@ int  tgo_copy_multi_distances(tgo_ctx* ctx, int32_t source, int64_t* dist_out);
 enum { TGO_TUNE_MS_SPLIT = 1, TGO_TUNE_MS_GHOST = 2, TGO_TUNE_DS_BINS = 3, TGO_TUNE_DS_PILE_CAP = 4,
        TGO_TUNE_DS_DONE = 5, TGO_TUNE_MS_COLD = 6, TGO_TUNE_DS_PULL = 7, TGO_TUNE_DS_SMALL = 8,
        TGO_TUNE_MS_STAY = 9, TGO_TUNE_MS_SPARSE = 10, TGO_TUNE_TRI_WAVE_ROW = 11,
-       TGO_TUNE_TRI_BLOCK_ROW = 12 };
+       TGO_TUNE_TRI_BLOCK_ROW = 12, TGO_TUNE_MS_HEAD = 13 };
 int  tgo_set_tuning(tgo_ctx* ctx, int32_t key, double value);
 
 /* ---- Tracing (the reference's only hook is FulgoraGraphComputer.java:143,307

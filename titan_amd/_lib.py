@@ -39,6 +39,7 @@ FLAG_STATS = 1
 TUNE_MS_SPLIT, TUNE_MS_GHOST, TUNE_DS_BINS, TUNE_DS_PILE_CAP, TUNE_DS_DONE, TUNE_MS_COLD, TUNE_DS_PULL = 1, 2, 3, 4, 5, 6, 7   # tgo_set_tuning keys
 TUNE_DS_SMALL = 8
 TUNE_MS_STAY, TUNE_MS_SPARSE = 9, 10
+TUNE_MS_HEAD = 13   # tgo_bfs_multi: entries of its own lists a long-list lane probes before the whole wave
 TUNE_TRI_WAVE_ROW, TUNE_TRI_BLOCK_ROW = 11, 12   # tgo_triangles: forward-row lengths of the wave / workgroup paths
 TRACE_JSON, TRACE_ROCTX = 1, 2   # tgo_trace_enable flags
 DIST_ABSENT = -(1 << 63)

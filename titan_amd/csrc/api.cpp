@@ -91,6 +91,7 @@ struct tgo_ctx {
                                 // hot head (and segment); < 0: TGO_MS_COLD / on
     double ms_stay = -1.0;      // tgo_set_tuning(TGO_TUNE_MS_STAY): gamma; < 0: TGO_MS_STAY / the default
     double ms_sparse = -1.0;    // tgo_set_tuning(TGO_TUNE_MS_SPARSE): fraction of n_active; < 0: TGO_MS_SPARSE / the default
+    int64_t ms_head = -1;       // tgo_set_tuning(TGO_TUNE_MS_HEAD): entries, 0 = off; < 0: TGO_MS_HEAD / the default
     int64_t tri_wave_row = -1;  // tgo_set_tuning(TGO_TUNE_TRI_WAVE_ROW / _BLOCK_ROW): forward-row lengths from
     int64_t tri_block_row = -1; // which a wave / a workgroup takes the row; < 0: the defaults (kTriWaveRow / kTriBlockRow)
     int64_t tri_max = 0;        // largest count of the last tgo_triangles (an Integer key's range check)
@@ -1273,7 +1274,7 @@ int finish_distance_program(tgo_ctx* ctx, int scope, int flags, int64_t* dist_ou
 
 // ============================================================================ C-ABI
 
-namespace tgo { double ms_split_of(const tgo_ctx* ctx); double ms_stay_of(const tgo_ctx* ctx); double ms_sparse_of(const tgo_ctx* ctx); int part_upload(tgo_ctx* ctx, HostGraph& h, int64_t n_global, int64_t lo); }
+namespace tgo { double ms_split_of(const tgo_ctx* ctx); double ms_stay_of(const tgo_ctx* ctx); double ms_sparse_of(const tgo_ctx* ctx); int64_t ms_head_of(const tgo_ctx* ctx); int part_upload(tgo_ctx* ctx, HostGraph& h, int64_t n_global, int64_t lo); }
 
 namespace {
 struct TrimTemps {                  // tmp_cache.cpp: nothing stays reserved between loads
@@ -1334,6 +1335,12 @@ int tgo_set_tuning(tgo_ctx* ctx, int32_t key, double value) {
         if (!((value >= 0.0 && value <= 1.0e18) || value == -1.0))
             return fail(ctx, TGO_E_INVALID, "TGO_TUNE_MS_SPARSE: a fraction >= 0 (0 = off) or -1 (the default)");
         ctx->ms_sparse = value;
+        return TGO_OK;
+    case TGO_TUNE_MS_HEAD:
+        if (!((value >= 0.0 && value <= static_cast<double>(kMsHeadMax)) || value == -1.0) ||
+            value != static_cast<double>(static_cast<int64_t>(value)))
+            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_MS_HEAD: a whole number of entries in [0, 2^20] (0 = off) or -1 (the default)");
+        ctx->ms_head = static_cast<int64_t>(value);
         return TGO_OK;
     case TGO_TUNE_DS_PILE_CAP:
         if (!(value >= 0.0) || value > 9.0e15) return fail(ctx, TGO_E_INVALID, "TGO_TUNE_DS_PILE_CAP: entries >= 0");
@@ -1749,6 +1756,9 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
     // and has at most that fraction of n_active entries (level 0 always) runs in the sparse
     // form (k_ms_push_sparse / k_ms_settle_sparse): no pass over every mask.
     const double stay_gamma = tgo::ms_stay_of(ctx), sparse_frac = tgo::ms_sparse_of(ctx);
+    // TGO_TUNE_MS_HEAD: the entries of its own lists a lane with a long list probes before the
+    // whole wave takes the list (0 = off)
+    const int64_t head = tgo::ms_head_of(ctx);
     int64_t qlen = static_cast<int64_t>(uniq.size());
     int64_t mf = 0;             // the seeds' entries are not read back: level 0 always pushes (a
                                 // direction is policy only; the read cost a stream drain, ~45 us)
@@ -1884,7 +1894,7 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
             count_open = stay_gamma > 0.0 && !cs.acc && mf < prev_mf;
             HIP_TRY(k_ms_pull(pull, push, g.n_active, full, fr, filter ? s.ms_fbm : nullptr, s.ms_vis, nx,
                               ms_planes(ctx), s.cnt, L + 1, st, filter ? filter_from : 0, full & ~sparse,
-                              sparse ? nx : nullptr, cs, count_open));
+                              sparse ? nx : nullptr, cs, count_open, cs.acc ? 0 : head));   // hot_lim's cut rule as it was
             if (cs.acc) {
                 HIP_TRY(k_ms_cold(g.msc_adj, g.msc_row, g.msc_C, fr, s.ms_need, s.ms_cacc, st));
                 HIP_TRY(k_ms_finish(push, g.n_active, full, s.ms_vis, nx, sparse ? nx : nullptr, ms_planes(ctx), s.cnt,
@@ -1981,11 +1991,14 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
         if (trace && count_open) std::fprintf(stderr, "[tgo]   %lld list entries of still-open vertices\n", (long long)mu);
         static const bool diag = env_double("TGO_MS_DIAG", 0.0) != 0.0;
         if (trace && diag && use_pull) {
-            unsigned long long d[10] = {};
+            unsigned long long d[kMsDiagWords] = {};
             HIP_TRY(k_ms_diag_take(d, st));
             std::fprintf(stderr, "[tgo]   pull: %llu entries examined, %llu hot / %llu cold mask gathers, %llu open vertices, "
                          "%llu stopped early; long lists: %llu, %llu entries examined (%llu hot / %llu cold gathers), "
                          "%llu stopped early\n", d[0], d[1], d[2], d[3], d[4], d[6], d[5], d[8], d[9], d[7]);
+            std::fprintf(stderr, "[tgo]   long lists covered within 4 / 8 / 16 / 32 / 64 entries: %llu / %llu / %llu / %llu / %llu, "
+                         "later %llu, never %llu (head %lld)\n", d[10], d[11], d[12], d[13], d[14], d[15], d[16],
+                         static_cast<long long>(head));
         }
         std::swap(fr, nx);
         cur ^= 1;
@@ -4141,6 +4154,16 @@ double ms_stay_of(const tgo_ctx* ctx) {
 double ms_sparse_of(const tgo_ctx* ctx) {
     static const double env = std::max(0.0, env_double("TGO_MS_SPARSE", kMsSparseDefault));
     return ctx->ms_sparse >= 0.0 ? ctx->ms_sparse : env;
+}
+// Head probe of ms_pull's long lists, in entries: the ctx's tgo_set_tuning value, else TGO_MS_HEAD,
+// else the default.
+int64_t ms_head_of(const tgo_ctx* ctx) {
+    static const int64_t env = [] {
+        const double v = env_double("TGO_MS_HEAD", static_cast<double>(kMsHeadDefault));
+        if (!(v >= 0.0)) return int64_t(0);                                  // negative or not a number
+        return static_cast<int64_t>(std::min(v, static_cast<double>(kMsHeadMax)));   // clamped before the cast
+    }();
+    return ctx->ms_head >= 0 ? ctx->ms_head : env;
 }
 
 }  // namespace tgo

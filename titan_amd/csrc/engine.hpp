@@ -770,11 +770,13 @@ hipError_t k_ds_apply(const View& push, const int64_t* recv, int64_t npairs, int
                       long long* track, hipStream_t s);
 hipError_t k_unpermute_i64(const int64_t* in, const int32_t* perm, int64_t* out, int64_t n, hipStream_t s);
 hipError_t k_ms_seed(const int64_t* seeds, int nseeds, uint64_t* vis, uint64_t* fr, int64_t fr_rows, hipStream_t s);
-hipError_t k_ms_diag_take(unsigned long long* out10, hipStream_t s);   // 10 diagnostic words
+constexpr int kMsDiagWords = 17;
+hipError_t k_ms_diag_take(unsigned long long* out, hipStream_t s);   // kMsDiagWords diagnostic words
 hipError_t k_ms_pull(const View& pull, const View& push, int64_t n_active, uint64_t full, const uint64_t* fr,
                      const uint64_t* fbm, uint64_t* vis, uint64_t* nx, LevelPlanes lvl, Counters* cnt,
                      int32_t next_level, hipStream_t s, int32_t filter_from, uint64_t dense = ~0ULL,
-                     const uint64_t* cand = nullptr, MsColdSplit cs = MsColdSplit(), bool count_open = false);
+                     const uint64_t* cand = nullptr, MsColdSplit cs = MsColdSplit(), bool count_open = false,
+                     int64_t head = 0);
 // the blocked cold pass and the settle of the rows it completed (msbfs.hip)
 hipError_t k_ms_cold(const int32_t* cadj, const int32_t* crow, int64_t C, const uint64_t* fr, const uint8_t* need,
                      uint64_t* acc, hipStream_t s);
@@ -808,6 +810,11 @@ hipError_t k_ms_push(const View& push, const int32_t* q, const int64_t* qpre, in
 // level with at most this fraction of n_active entries runs sparse): DESIGN.md §4.1.
 constexpr double kMsStayDefault = 4.0;
 constexpr double kMsSparseDefault = 1.0 / 16.0;
+// Default of TGO_TUNE_MS_HEAD: the entries of its own lists a lane with a long list (degree >
+// kCoop) probes before the whole wave takes the list (ms_pull's head): one trip
+// of the lane's own walk.
+constexpr int64_t kMsHeadDefault = 4;
+constexpr int64_t kMsHeadMax = 1 << 20;
 // Sparse push level (one GPU): nx all zero beforehand; the touched vertices — exactly the next
 // frontier — are appended to qn (length in cnt->qlen, no particular order), and
 // k_ms_settle_sparse settles them over that list (length read on the device): vis, levels,

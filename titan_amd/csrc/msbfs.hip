@@ -98,11 +98,74 @@ __device__ __forceinline__ bool maybe_frontier(const uint64_t* __restrict__ fbm,
 // Diagnostic tallies of a pull level (TGO_MS_DIAG=1 with TGO_TRACE=1; off in the product):
 // [0] list entries examined, [1] mask gathers of hot neighbours (u < kDiagHot), [2] of cold
 // ones, [3] open vertices, [4] open vertices whose walk stopped early (every open source covered);
-// long lists (wave-cooperative): [5] entries examined, [6] lists, [7] lists that stopped early,
-// [8] / [9] their hot / cold mask gathers
+// long lists (degree > coop): [5] entries examined, [6] lists, [7] lists that stopped early,
+// [8] / [9] their hot / cold mask gathers; [10..16] where a long list's walk was covered, as a
+// position in its concatenated lists: within 4, 8, 16, 32, 64 entries, later, never (exact to the
+// entry in the whole-wave loop at kLong = 1, to the end of the trip in the head probe)
 constexpr int32_t kDiagHot = 393216;
-constexpr int kDiagWords = 10;
+constexpr int kDiagWords = kMsDiagWords;
 __device__ unsigned long long g_ms_diag[kDiagWords];
+__device__ __forceinline__ int diag_cover_bucket(int64_t pos) {
+    return pos <= 4 ? 10 : pos <= 8 ? 11 : pos <= 16 ? 12 : pos <= 32 ? 13 : pos <= 64 ? 14 : 15;
+}
+
+// One lane's walk of its own lists: from k0 in list 0, then from k1 in list 1, at most lim
+// entries in all, until every source of `want` is covered.  k0 / k1 come back as the positions
+// the walk reached, so that a later walk goes on from there.  kStep entries per dependent round
+// trip: their index loads issue together, then their bitmap probes, then their mask gathers
+// (lists rarely cover every open source early).  No branch inside a trip: positions past the end
+// re-read the last entry, a filtered entry gathers mask 0's line (one L1 line for the wave) and
+// drops it — a conditional load per entry made the compiler wait for every outstanding load
+// before the next, one load in flight per lane.  cut: a list went on past hot_lim (the lists
+// are sorted, so the walk of that list ends there).  dg_ent / dg_hot: the diagnostic words of
+// the entries and of the hot gathers (the cold ones' follows).
+template <int kStep, bool kDiag>
+__device__ __forceinline__ void walk_own(const View& pull, int64_t& k0, int64_t e0, int64_t& k1, int64_t e1, int64_t lim,
+        uint64_t want, const uint64_t* __restrict__ fr, const uint64_t* __restrict__ fbm, int32_t filter_from,
+        int32_t hot_lim, uint64_t& acc, bool& cut, unsigned long long* dg, int dg_ent, int dg_hot) {
+    for (int l = 0; l < 2 && lim > 0 && (acc & want) != want; ++l) {
+        const int32_t* adj = l == 0 ? pull.adj0 : pull.adj1;
+        const int64_t from = l == 0 ? k0 : k1, end = l == 0 ? e0 : e1;
+        const int64_t e = end - from > lim ? from + lim : end;
+        bool cutl = false;
+        int64_t k = from;
+        for (; k < e && (acc & want) != want && !cutl; k += kStep) {
+            int32_t u[kStep];
+            bool ok[kStep], f[kStep];
+#pragma unroll
+            for (int j = 0; j < kStep; ++j) {
+                u[j] = __builtin_nontemporal_load(adj + min(k + j, e - 1));
+                const bool in = k + j < e;
+                cutl |= in && u[j] >= hot_lim;
+                ok[j] = in && u[j] < hot_lim;
+                f[j] = ok[j];
+            }
+            if (fbm) {                                        // kernel-uniform
+                uint64_t bw[kStep];
+#pragma unroll
+                for (int j = 0; j < kStep; ++j) bw[j] = fbm[(f[j] && u[j] >= filter_from ? u[j] : 0) >> 6];
+#pragma unroll
+                for (int j = 0; j < kStep; ++j)
+                    f[j] = f[j] && (u[j] < filter_from || ((bw[j] >> (u[j] & 63)) & 1ULL));
+            }
+            uint64_t mk[kStep];
+#pragma unroll
+            for (int j = 0; j < kStep; ++j) mk[j] = fr[f[j] ? u[j] : 0];
+            uint64_t m = 0;
+#pragma unroll
+            for (int j = 0; j < kStep; ++j) m |= f[j] ? mk[j] : 0ULL;
+            acc |= m;
+            if (kDiag)
+                for (int j = 0; j < kStep; ++j)
+                    if (ok[j]) { ++dg[dg_ent]; ++dg[u[j] < kDiagHot ? dg_hot : dg_hot + 1]; }
+        }
+        const int64_t reached = min(k, e);
+        lim -= reached - from;
+        if (l == 0) k0 = reached; else k1 = reached;
+        cut |= cutl;
+    }
+}
+
 // kStep: entries per dependent round trip of a lane's own list; kLong: entries per lane per
 // trip of a wave-cooperative long list (kLong * 64 per trip)
 // cs (MsColdSplit, hot_lim < INT32_MAX): the walk reads only neighbours < hot_lim (lists are
@@ -111,16 +174,20 @@ __device__ unsigned long long g_ms_diag[kDiagWords];
 // written (ms_cold ORs its cold neighbours in, ms_finish settles it).
 // kRamp: a long list's first trip reads 64 entries only (its head of hubs often covers every
 // open source), the later ones kLong * 64.
+// head: every lane with a long list first walks the first `head` entries of its own lists like a
+// short one (the lists are sorted hubs first: the masks that cover a walk are mostly among its
+// first entries), all long lists of the word at once; only the lanes still uncovered take the
+// whole wave, one list after another, from the position the head reached.  0 = off.
 // count_open: also sum the list entries of the vertices still open after the level (cnt->open; the
 // rows a cold split leaves to ms_finish are not in it).
 template <int kStep, bool kDiag = false, int kLong = 4, bool kRamp = false>
 __global__ void __launch_bounds__(kBlock) ms_pull(View pull, View push, int64_t n_active, uint64_t full,
         const uint64_t* __restrict__ fr, const uint64_t* __restrict__ fbm, uint64_t* __restrict__ vis,
         uint64_t* __restrict__ nx, LevelPlanes lvl, Counters* cnt, int32_t next_level, int32_t filter_from,
-        uint64_t dense, const uint64_t* __restrict__ cand, MsColdSplit cs, int64_t coop, bool count_open) {
+        uint64_t dense, const uint64_t* __restrict__ cand, MsColdSplit cs, int64_t coop, bool count_open, int64_t head) {
     const int32_t hot_lim = cs.hot_lim;
     unsigned long long nv = 0, mf = 0, bits = 0, mu = 0;
-    unsigned long long dg[kDiagWords] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long dg[kDiagWords] = {};
     const int64_t words = (n_active + 63) >> 6;
     // wave w of the block takes word b + w; words past the end run as all-closed lanes.  No
     // block barrier inside: the next frontier is only counted here (ms_queue builds its queue
@@ -139,62 +206,30 @@ __global__ void __launch_bounds__(kBlock) ms_pull(View pull, View push, int64_t 
             if (pull.nlists > 1) { b1 = pull.off1[v]; e1 = pull.off1[v + 1]; }
         }
         const int64_t deg = (e0 - b0) + (e1 - b1);
+        const bool is_big = want != 0 && deg > coop;
         uint64_t acc = 0;
         bool cut = false;                                     // a list went on past hot_lim
-        if (want && deg <= coop) {
-            for (int l = 0; l < 2 && (acc & want) != want; ++l) {
-                const int32_t* adj = l == 0 ? pull.adj0 : pull.adj1;
-                const int64_t e = l == 0 ? e0 : e1;
-                bool cutl = false;
-                // kStep entries per dependent round trip: their index loads issue together,
-                // then their bitmap probes, then their mask gathers (lists rarely cover every
-                // open source early).  No branch inside a trip: positions past the list re-read
-                // its last entry, a filtered entry gathers mask 0's line (one L1 line for the
-                // wave) and drops it — a conditional load per entry made the compiler wait for
-                // every outstanding load before the next, one load in flight per lane
-                for (int64_t k = l == 0 ? b0 : b1; k < e && (acc & want) != want && !cutl; k += kStep) {
-                    int32_t u[kStep];
-                    bool ok[kStep], f[kStep];
-#pragma unroll
-                    for (int j = 0; j < kStep; ++j) {
-                        u[j] = __builtin_nontemporal_load(adj + min(k + j, e - 1));
-                        const bool in = k + j < e;
-                        cutl |= in && u[j] >= hot_lim;
-                        ok[j] = in && u[j] < hot_lim;
-                        f[j] = ok[j];
-                    }
-                    if (fbm) {                                        // kernel-uniform
-                        uint64_t bw[kStep];
-#pragma unroll
-                        for (int j = 0; j < kStep; ++j) bw[j] = fbm[(f[j] && u[j] >= filter_from ? u[j] : 0) >> 6];
-#pragma unroll
-                        for (int j = 0; j < kStep; ++j)
-                            f[j] = f[j] && (u[j] < filter_from || ((bw[j] >> (u[j] & 63)) & 1ULL));
-                    }
-                    uint64_t mk[kStep];
-#pragma unroll
-                    for (int j = 0; j < kStep; ++j) mk[j] = fr[f[j] ? u[j] : 0];
-                    uint64_t m = 0;
-#pragma unroll
-                    for (int j = 0; j < kStep; ++j) m |= f[j] ? mk[j] : 0ULL;
-                    acc |= m;
-                    if (kDiag)
-                        for (int j = 0; j < kStep; ++j)
-                            if (ok[j]) { ++dg[0]; ++dg[u[j] < kDiagHot ? 1 : 2]; }
-                }
-                cut |= cutl;
-            }
-            if (kDiag) { ++dg[3]; if ((acc & want) == want) ++dg[4]; }
+        int64_t h0 = b0, h1 = b1;                             // where the lane's own walk stands
+        // short lists to their end and the heads of the long ones in the same trips
+        if (want)
+            walk_own<kStep, kDiag>(pull, h0, e0, h1, e1, is_big ? head : INT64_MAX, want, fr, fbm, filter_from, hot_lim,
+                                   acc, cut, dg, is_big ? 5 : 0, is_big ? 8 : 1);
+        const bool head_done = is_big && (acc & want) == want;   // covered within the head
+        if (kDiag) {
+            if (want && !is_big) { ++dg[3]; if ((acc & want) == want) ++dg[4]; }
+            if (head_done) { ++dg[6]; ++dg[7]; ++dg[diag_cover_bucket((h0 - b0) + (h1 - b1))]; }
         }
-        unsigned long long big = __ballot(want != 0 && deg > coop);
+        unsigned long long big = __ballot(is_big && !head_done);
         while (big) {
             const int src = __ffsll(static_cast<long long>(big)) - 1;
             big &= big - 1;
             const uint64_t wsrc = __shfl(want, src, 64);
-            uint64_t a = 0;
+            uint64_t a = __shfl(acc, src, 64);                // what the head found
             bool wcut = false;                                // wave-uniform
+            int64_t pos = kDiag ? __shfl((h0 - b0) + (h1 - b1), src, 64) : 0;   // entries before this trip
+            int64_t cover = -1;                               // diagnostics: the entry that covered the walk
             for (int l = 0; l < 2; ++l) {
-                const int64_t bb = __shfl(l == 0 ? b0 : b1, src, 64);
+                const int64_t bb = __shfl(l == 0 ? h0 : h1, src, 64);
                 const int64_t ee = __shfl(l == 0 ? e0 : e1, src, 64);
                 const int32_t* adj = l == 0 ? pull.adj0 : pull.adj1;
                 bool done = false;
@@ -209,6 +244,7 @@ __global__ void __launch_bounds__(kBlock) ms_pull(View pull, View push, int64_t 
                         u[j] = (j < jl && x < ee) ? __builtin_nontemporal_load(adj + x) : -1;
                         if (u[j] >= hot_lim) { u[j] = -1; hc = true; }
                     }
+                    const int64_t trip = min(static_cast<int64_t>(jl) * 64, ee - k);
                     k += static_cast<int64_t>(jl) * 64;
                     first = false;
                     if (__ballot(hc)) { done = true; wcut = true; }   // the rest of the list is cold
@@ -219,6 +255,17 @@ __global__ void __launch_bounds__(kBlock) ms_pull(View pull, View push, int64_t 
 #pragma unroll
                     for (int j = 0; j < kLong; ++j)
                         if (f[j]) m |= fr[u[j]];
+                    if (kDiag && cover < 0) {
+                        // the first lane at which the masks up to it cover the walk
+                        uint64_t p = m;
+                        for (int o = 1; o < 64; o <<= 1) {
+                            const uint64_t y = __shfl_up(p, o, 64);
+                            if (lane() >= o) p |= y;
+                        }
+                        const unsigned long long cv = __ballot(((a | p) & wsrc) == wsrc);
+                        if (cv) cover = pos + (kLong == 1 ? __ffsll(static_cast<long long>(cv)) : trip);
+                        pos += trip;
+                    }
                     for (int off = 32; off > 0; off >>= 1) m |= __shfl_xor(m, off, 64);
                     if (kDiag)
                         for (int j = 0; j < kLong; ++j)
@@ -233,7 +280,11 @@ __global__ void __launch_bounds__(kBlock) ms_pull(View pull, View push, int64_t 
             if (lane() == src) {
                 acc = a;
                 cut = wcut;
-                if (kDiag) { ++dg[6]; if ((a & wsrc) == wsrc) ++dg[7]; }
+                if (kDiag) {
+                    ++dg[6];
+                    if ((a & wsrc) == wsrc) ++dg[7];
+                    ++dg[(a & wsrc) == wsrc && cover >= 0 ? diag_cover_bucket(cover) : 16];
+                }
             }
         }
         if (cut && (acc & want) != want && v < n_active) {   // left to the cold pass
@@ -1044,7 +1095,7 @@ hipError_t k_ms_seed(const int64_t* seeds, int nseeds, uint64_t* vis, uint64_t* 
 hipError_t k_ms_pull(const View& pull, const View& push, int64_t n_active, uint64_t full, const uint64_t* fr,
                      const uint64_t* fbm, uint64_t* vis, uint64_t* nx, LevelPlanes lvl, Counters* cnt,
                      int32_t next_level, hipStream_t s, int32_t filter_from, uint64_t dense, const uint64_t* cand,
-                     MsColdSplit cs, bool count_open) {
+                     MsColdSplit cs, bool count_open, int64_t head) {
     // TGO_MS_STEP: entries a lane loads per round trip of its own list (4 default since the
     // trips are branch-free, round 6: sweep 3.623 -> 3.562 ms against 8 with the branchy trips,
     // profiles/r06ms1_ms_branchfree_ab.log; 8 / 16 probes)
@@ -1060,8 +1111,8 @@ hipError_t k_ms_pull(const View& pull, const View& push, int64_t n_active, uint6
     static const int64_t coop = [] { const char* e = std::getenv("TGO_MS_COOP"); return e ? std::atoll(e) : kCoop; }();
     const dim3 grid(grid_for(n_active, 8192));
 #define TGO_MS_PULL(S, D, LG, R) ms_pull<S, D, LG, R><<<grid, kBlock, 0, s>>>(pull, push, n_active, full, fr, fbm, vis, \
-        nx, lvl, cnt, next_level, filter_from, dense, cand, cs, coop, count_open)
-    if (diag) TGO_MS_PULL(8, true, 1, false);
+        nx, lvl, cnt, next_level, filter_from, dense, cand, cs, coop, count_open, head)
+    if (diag) TGO_MS_PULL(4, true, 1, false);                // the product's trips, with the tallies
     else if (ramp) TGO_MS_PULL(8, false, 4, true);
     else if (step == 4 && lng == 1) TGO_MS_PULL(4, false, 1, false);
     else if (step == 16 && lng == 1) TGO_MS_PULL(16, false, 1, false);
@@ -1101,7 +1152,7 @@ hipError_t k_low_rows(const uint64_t* key, int64_t m, int32_t* row, hipStream_t 
     return hipGetLastError();
 }
 // The pull diagnostics since the last call (zeroed after the read).
-hipError_t k_ms_diag_take(unsigned long long* out, hipStream_t s) {  // kDiagWords (10) words
+hipError_t k_ms_diag_take(unsigned long long* out, hipStream_t s) {  // kDiagWords (kMsDiagWords) words
     hipError_t e = hipMemcpyFromSymbolAsync(out, HIP_SYMBOL(g_ms_diag), kDiagWords * sizeof(unsigned long long), 0,
                                             hipMemcpyDeviceToHost, s);
     if (e != hipSuccess) return e;

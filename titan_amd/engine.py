@@ -298,7 +298,8 @@ class Engine:
         """tgo_set_tuning: a traversal policy of this ctx (L.TUNE_MS_SPLIT: the multi-source
         source-split budget; < 0 restores the default; L.TUNE_MS_STAY: gamma of the sweep's
         stay-in-pull rule, 0 = off; L.TUNE_MS_SPARSE: the entry fraction of the rows with entries
-        up to which a push level runs in the sparse form, 0 = never; -1 restores either default).
+        up to which a push level runs in the sparse form, 0 = never; -1 restores either default;
+        L.TUNE_MS_HEAD: entries a long-list vertex of a pull level probes by itself, 0 = off).
         Never changes a result."""
         _check(self.lib, self.ctx, self.lib.tgo_set_tuning(self.ctx, int(key), float(value)))
         return self
