@@ -1,4 +1,5 @@
-// api.cpp — the C-ABI (include/titan_gpu_olap.h): context, loads, program drivers.
+// api.cpp — the C-ABI (include/titan_gpu_olap.h): context, loads, program drivers (the
+// traversals are in api_traverse.cpp and api_msbfs.cpp; ctx.hpp holds what the files share).
 //
 // The program drivers replace FulgoraGraphComputer.submit's superstep loop
 // (FulgoraGraphComputer.java:151-189): instead of one full edgestore scan per superstep,
@@ -18,153 +19,11 @@
 #include <unordered_map>
 #include <hip/hip_runtime_api.h>
 #include "codec.hpp"
-#include "engine.hpp"
-#include "trace.hpp"
-#include "../../include/titan_gpu_olap_part.h"
+#include "ctx.hpp"
 
 using namespace tgo;
 
-struct tgo_ctx {
-    tgo_options opts{};
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    std::string err;
-    RowStaging staging;
-    DevGraph g;
-    bool loaded = false;
-    std::vector<int64_t> titan_id;
-    std::vector<int32_t> perm;                       // row-order dense -> internal
-    // Titan id -> dense (seed lookups, tgo_dense_ids): binary search over titan_id when it is
-    // strictly increasing (edge loads; row loads of an ordered scan usually), else over a
-    // sorted copy built on the first lookup — no per-load hash map (16.8 M inserts at RMAT-24)
-    bool id_sorted = false;
-    std::vector<std::pair<int64_t, int32_t>> id_index;
-    Scratch sc;
-    tgo_stats st{};
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    int64_t dev_bytes = 0;
-    std::vector<void*> allocs;
-    int part_cur = 0;           // partitioned BFS: queue buffer holding the frontier
-    int64_t part_qlen = 0;      // its length
-    bool part_queued = true;    // q[part_cur] holds the frontier (pull / bottom-up levels only count it)
-    // native multi-source sweep (part_driver.cpp): this rank's slice of the candidate words is
-    // not packed but ORed in directly (tgo::part_ms_bypass); -1 = every slice packed
-    int part_ms_self = -1;
-    uint64_t* part_ms_cand = nullptr;
-    const uint64_t* part_frontier = nullptr;   // after bottom-up: the caller's nb_local (queued lazily)
-    int64_t* part_dcounts = nullptr;    // caller's device counts (tgo_part_device_counts)
-    int64_t* part_qlen_dev = nullptr;   // device copy of the queue length (lazy host read)
-    bool part_qlen_stale = false;       // part_qlen must be read from part_qlen_dev
-    double part_alpha = 0.85, part_base = 0.0;
-    int32_t part_pr_iter = 0;   // partitioned PageRank: iteration reached / program length
-    int32_t part_pr_iters = 0;
-    int32_t part_pr_world = 0;  // blocked gathered layout (tgo_part_pr_blocked): world, H, A
-    bool part_pr_plain = false; // tgo_part_pr_plain: the plain layout although the blocked one is built
-    int64_t part_pr_hot = 0, part_pr_span = 0;
-    int64_t part_relaxed = 0;   // partitioned SSSP: entries relaxed, phases
-    int32_t part_phases = 0;
-    int64_t part_seed = -1;     // partitioned SSSP: the seed's internal id when owned here
-    bool part_split = false;    // partitioned SSSP run on the light/heavy split (part_sssp_split)
-    bool part_devloop = false;  // ... and on the device-sized loop (delta_loop.hip, part_sssp_dev_*)
-    EdgeProg edge_prog;         // tgo_set_edge_program (TGO_EDGE_PROGRAM gathers)
-    int64_t pv_max_out = 0, pv_max_in = 0;   // largest OUT / IN list of a vertex cut
-    std::vector<int64_t> pv_rows;            // row ids of the vertex cuts
-    // last finished program whose compute keys tgo_result_rows can encode (-1 = none)
-    int res_kind = -1;
-    bool host_decode = false;                // TGO_HOST_DECODE latched for the load in progress
-    DecodeScratch dec;                       // device row decoder buffers (decode.hip)
-    bool res_empty = false;                  // it set no property (PageRank iterations(0))
-    ResultSource res_src;
-    int num_cus = 256;          // compute units of the device (persistent launches)
-    double ms_split = -1.0;     // tgo_set_tuning(TGO_TUNE_MS_SPLIT); < 0: TGO_MS_SPLIT / the default
-    int ms_ghost = 1;           // tgo_set_tuning(TGO_TUNE_MS_GHOST): dense partitioned levels exchange ghosts
-    int ds_bins = -1;           // tgo_set_tuning(TGO_TUNE_DS_BINS): 1 / 0; < 0: TGO_DS_BINS / on
-    int64_t ds_pile_cap = 0;    // tgo_set_tuning(TGO_TUNE_DS_PILE_CAP): entries per pile; 0 = n
-    int ds_done = -1;           // tgo_set_tuning(TGO_TUNE_DS_DONE): 1 / 0; < 0: TGO_DS_DONE / off
-    double ds_pull = -1;        // tgo_set_tuning(TGO_TUNE_DS_PULL): member fraction; < 0: TGO_DS_PULL / off
-    int ds_small = -1;          // tgo_set_tuning(TGO_TUNE_DS_SMALL): 1 / 0; < 0: TGO_DS_SMALL / off
-    unsigned long long* part_srcent = nullptr;   // next settle's per-source sums (part_ms_settle_sums)
-    bool part_count_only = false;               // next settle: no queue (part_ms_settle_sums)
-    uint64_t* part_own_next = nullptr;          // next push: owned targets straight into these masks
-    uint64_t* part_own_direct = nullptr;        // the last push did so (its settle skips the own OR)
-    int64_t ms_cold = -1;       // tgo_set_tuning(TGO_TUNE_MS_COLD): 0 off, 1 on, > 1 on with that
-                                // hot head (and segment); < 0: TGO_MS_COLD / on
-    double ms_stay = -1.0;      // tgo_set_tuning(TGO_TUNE_MS_STAY): gamma; < 0: TGO_MS_STAY / the default
-    double ms_sparse = -1.0;    // tgo_set_tuning(TGO_TUNE_MS_SPARSE): fraction of n_active; < 0: TGO_MS_SPARSE / the default
-    int64_t ms_head = -1;       // tgo_set_tuning(TGO_TUNE_MS_HEAD): entries, 0 = off; < 0: TGO_MS_HEAD / the default
-    int64_t tri_wave_row = -1;  // tgo_set_tuning(TGO_TUNE_TRI_WAVE_ROW / _BLOCK_ROW): forward-row lengths from
-    int64_t tri_block_row = -1; // which a wave / a workgroup takes the row; < 0: the defaults (kTriWaveRow / kTriBlockRow)
-    int64_t tri_max = 0;        // largest count of the last tgo_triangles (an Integer key's range check)
-    // state a native partitioned driver keeps between runs on this graph (part_driver.cpp:
-    // the PageRank ghost lists); dropped with the graph
-    std::shared_ptr<void> part_state;
-};
-
-namespace {
-
-double env_double(const char* name, double dflt) {
-    const char* v = std::getenv(name);
-    return v ? std::atof(v) : dflt;
-}
-
-int fail(tgo_ctx* c, int code, const std::string& msg) {
-    if (c) c->err = msg;
-    return code;
-}
-
-#define HIP_TRY(call)                                                              \
-    do {                                                                           \
-        hipError_t e__ = (call);                                                   \
-        if (e__ != hipSuccess)                                                     \
-            return fail(ctx, e__ == hipErrorOutOfMemory ? TGO_E_OOM : TGO_E_HIP,   \
-                        std::string(#call) + ": " + hipGetErrorString(e__));       \
-    } while (0)
-
-template <class T>
-hipError_t dev_alloc(tgo_ctx* ctx, T*& p, int64_t count) {
-    void* q = nullptr;
-    const size_t bytes = static_cast<size_t>(std::max<int64_t>(count, 1)) * sizeof(T);
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) return e;
-    ctx->allocs.push_back(q);
-    ctx->dev_bytes += static_cast<int64_t>(bytes);
-    p = static_cast<T*>(q);
-    return hipSuccess;
-}
-
-// Release one dev_alloc array of `count` elements before the graph goes (the stream is
-// synchronised first: queued kernels may still use it).
-template <class T>
-void dev_free(tgo_ctx* ctx, T*& p, int64_t count) {
-    if (!p) return;
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    auto it = std::find(ctx->allocs.begin(), ctx->allocs.end(), static_cast<void*>(p));
-    if (it != ctx->allocs.end()) {
-        ctx->allocs.erase(it);
-        ctx->dev_bytes -= static_cast<int64_t>(std::max<int64_t>(count, 1) * sizeof(T));
-        (void)hipFree(p);
-    }
-    p = nullptr;
-}
-
-// Adopt a device array built on the device (DevArray): no copy, freed with the graph.
-template <class T>
-void adopt(tgo_ctx* ctx, T*& p, DevArray<T>& a) {
-    p = a.p;
-    if (a.p) {
-        ctx->allocs.push_back(a.p);
-        ctx->dev_bytes += static_cast<int64_t>(std::max<int64_t>(a.n, 1) * sizeof(T));
-    }
-    a.p = nullptr;
-    a.n = -1;
-}
-
-template <class T>
-hipError_t upload(tgo_ctx* ctx, T*& p, const std::vector<T>& h) {
-    hipError_t e = dev_alloc(ctx, p, static_cast<int64_t>(h.size()));
-    if (e != hipSuccess || h.empty()) return e;
-    return copy_chunked(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-}
+namespace tgo {
 
 void free_graph(tgo_ctx* ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
@@ -190,15 +49,68 @@ int threads_of(const tgo_ctx* ctx) {
     return std::max(1, std::min(t, 64));
 }
 
+// Row-order dense index of a Titan id, -1 when no executed vertex has it.
+int64_t dense_of(tgo_ctx* ctx, int64_t id) {
+    const std::vector<int64_t>& t = ctx->titan_id;
+    if (ctx->id_sorted) {
+        const auto it = std::lower_bound(t.begin(), t.end(), id);
+        return it != t.end() && *it == id ? static_cast<int64_t>(it - t.begin()) : -1;
+    }
+    if (ctx->id_index.size() != t.size()) {
+        ctx->id_index.resize(t.size());
+        for (size_t v = 0; v < t.size(); ++v) ctx->id_index[v] = {t[v], static_cast<int32_t>(v)};
+        std::sort(ctx->id_index.begin(), ctx->id_index.end());
+    }
+    const auto it = std::lower_bound(ctx->id_index.begin(), ctx->id_index.end(), std::make_pair(id, INT32_MIN));
+    return it != ctx->id_index.end() && it->first == id ? it->second : -1;
+}
+
+int resolve_seed(tgo_ctx* ctx, int64_t seed, int is_dense, int64_t& out) {
+    if (is_dense) {
+        if (seed < 0 || seed >= ctx->g.n) return fail(ctx, TGO_E_INVALID, "dense seed out of range");
+        out = ctx->perm[seed];
+        return TGO_OK;
+    }
+    const int64_t d = dense_of(ctx, seed);
+    out = d < 0 ? -1 : ctx->perm[d];                                 // unknown seed: nobody gets a distance
+    return TGO_OK;
+}
+
+int check_program(tgo_ctx* ctx, int scope) {
+    if (!ctx->loaded) return fail(ctx, TGO_E_STATE, "no graph loaded");
+    if (scope < 0 || scope > 2) return fail(ctx, TGO_E_INVALID, "invalid scope");
+    if (scope != ctx->g.scope)
+        return fail(ctx, TGO_E_INVALID, "program scope differs from the scope the graph was loaded (preloaded) for");
+    return TGO_OK;
+}
+
+// wait_publish for a publish that later ones may have overwritten: spin until the sequence
+// word reaches seq (the words then hold that publish or a later one).
+int wait_publish_at_least(tgo_ctx* ctx, unsigned long long seq) {
+    Scratch& s = ctx->sc;
+    const volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(s.hcnt) + kCounterWords;
+    for (uint64_t it = 1;; ++it) {
+        if (*flag >= seq) break;
+        if ((it & 0x3FFF) == 0) {
+            const hipError_t q = hipStreamQuery(ctx->stream);
+            if (q != hipSuccess && q != hipErrorNotReady) return fail(ctx, TGO_E_HIP, hipGetErrorString(q));
+            if (q == hipSuccess && *flag < seq) return fail(ctx, TGO_E_HIP, "loop state publish not visible after the stream drained");
+        }
+        __builtin_ia32_pause();
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return TGO_OK;
+}
+
+}  // namespace tgo
+
+namespace {
+
 // Cache-blocked PageRank in-lists (ColdBlocks, engine.hpp) for one-GPU PageRank.
 // TGO_PR_BLOCKED=0 turns it off; TGO_PR_HOT / TGO_PR_SEG set the hot threshold and the cold
 // segment size in sources (defaults: 384 K sources = 3 MB of fp64 messages each, under one
 // XCD's 4 MB L2 so the row streams do not evict the head; swept on RMAT-24 in
 // profiles/r02m_pr_probe.log and profiles/r02an_pr_hot_seg_probe*.log).
-int64_t env_i64(const char* name, int64_t dflt) {
-    const char* v = std::getenv(name);
-    return v ? std::atoll(v) : dflt;
-}
 constexpr int64_t kPrSegDefault = 393216;   // 3 MB (profiles/r02an_pr_hot_seg_probe*.log)
 // hot head: 3 MB for the slot tiles; 6 MB for the fixed-point super-tiles, whose source-sorted
 // 380 K-entry tiles reuse lines enough that a head past one XCD's L2 still pays (RMAT-24
@@ -318,7 +230,7 @@ int upload_cold_blocks(tgo_ctx* ctx, const std::vector<int64_t>& off, const std:
     cb = ColdBlocks();
     ready = false;
     HostColdBlocks hc;
-    static const bool trace = env_i64("TGO_TRACE", 0) != 0;
+    static const bool trace = trace_on();
     auto t_last = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
         if (!trace && !tracing()) return;
@@ -333,7 +245,7 @@ int upload_cold_blocks(tgo_ctx* ctx, const std::vector<int64_t>& off, const std:
     // TGO_PR_FX_COLD (default on): fixed-point cold blocks (spmv.hip cold_fx) of up to 4096
     // pieces and TGO_PR_FX_CE entries
     const bool cold_fx = env_i64("TGO_PR_FX", 1) != 0 && env_i64("TGO_PR_FX_COLD", 1) != 0 && win == 0;
-    if (d_off && d_adj && env_i64("TGO_HOST_ASSEMBLY", 0) == 0) {
+    if (d_off && d_adj && !host_assembly()) {
         std::string err;
         if (int rc = build_cold_blocks_device(d_off, d_adj, static_cast<int64_t>(off.size()) - 1, d_nnz, n_src, hot,
                                               env_i64("TGO_PR_SEG", kPrSegDefault),
@@ -537,7 +449,7 @@ int fx_take_bad(tgo_ctx* ctx, ColdBlocks& cb, bool* bad) {
 int upload_graph(tgo_ctx* ctx, HostGraph& h, bool allow_segments = true) {
     DevGraph& g = ctx->g;
     // TGO_TRACE=1: per-phase load times on stderr
-    static const bool trace = env_i64("TGO_TRACE", 0) != 0;
+    static const bool trace = trace_on();
     auto t_last = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
         if (!trace && !tracing()) return;
@@ -680,601 +592,9 @@ int upload_graph(tgo_ctx* ctx, HostGraph& h, bool allow_segments = true) {
     return TGO_OK;
 }
 
-// Views of the loaded scope.
-View make_view(const DevCsr* a, const DevCsr* b) {
-    View v{};
-    v.off0 = a->off; v.adj0 = a->adj; v.w0 = a->w;
-    if (b) { v.off1 = b->off; v.adj1 = b->adj; v.w1 = b->w; v.nlists = 2; }
-    else { v.off1 = a->off; v.adj1 = a->adj; v.w1 = a->w; v.nlists = 1; }
-    return v;
-}
-View pull_view(const DevGraph& g, int scope) {
-    if (scope == TGO_SCOPE_IN_E) return make_view(&g.out, nullptr);
-    if (scope == TGO_SCOPE_OUT_E) return make_view(&g.in, nullptr);
-    return make_view(&g.out, &g.in);
-}
-View push_view(const DevGraph& g, int scope) {
-    if (g.has_transpose) return make_view(&g.push_t, nullptr);
-    if (scope == TGO_SCOPE_IN_E) return make_view(&g.in, nullptr);
-    if (scope == TGO_SCOPE_OUT_E) return make_view(&g.out, nullptr);
-    return make_view(&g.out, &g.in);
-}
-
-// Row-order dense index of a Titan id, -1 when no executed vertex has it.
-int64_t dense_of(tgo_ctx* ctx, int64_t id) {
-    const std::vector<int64_t>& t = ctx->titan_id;
-    if (ctx->id_sorted) {
-        const auto it = std::lower_bound(t.begin(), t.end(), id);
-        return it != t.end() && *it == id ? static_cast<int64_t>(it - t.begin()) : -1;
-    }
-    if (ctx->id_index.size() != t.size()) {
-        ctx->id_index.resize(t.size());
-        for (size_t v = 0; v < t.size(); ++v) ctx->id_index[v] = {t[v], static_cast<int32_t>(v)};
-        std::sort(ctx->id_index.begin(), ctx->id_index.end());
-    }
-    const auto it = std::lower_bound(ctx->id_index.begin(), ctx->id_index.end(), std::make_pair(id, INT32_MIN));
-    return it != ctx->id_index.end() && it->first == id ? it->second : -1;
-}
-
-int resolve_seed(tgo_ctx* ctx, int64_t seed, int is_dense, int64_t& out) {
-    if (is_dense) {
-        if (seed < 0 || seed >= ctx->g.n) return fail(ctx, TGO_E_INVALID, "dense seed out of range");
-        out = ctx->perm[seed];
-        return TGO_OK;
-    }
-    const int64_t d = dense_of(ctx, seed);
-    out = d < 0 ? -1 : ctx->perm[d];                                 // unknown seed: nobody gets a distance
-    return TGO_OK;
-}
-
-int check_program(tgo_ctx* ctx, int scope) {
-    if (!ctx->loaded) return fail(ctx, TGO_E_STATE, "no graph loaded");
-    if (scope < 0 || scope > 2) return fail(ctx, TGO_E_INVALID, "invalid scope");
-    if (scope != ctx->g.scope)
-        return fail(ctx, TGO_E_INVALID, "program scope differs from the scope the graph was loaded (preloaded) for");
-    return TGO_OK;
-}
-
-// Counters of the work queued so far, without a copy + stream synchronisation: the publish
-// kernel stores them and then a sequence number into host-mapped memory; the host spins on
-// the sequence number (the level loops read a few words per level, so the wake-up latency of
-// a blocking synchronisation dominated short levels).  A stream error ends the spin.
-int wait_publish(tgo_ctx* ctx, unsigned long long seq);
-
-int read_counters(tgo_ctx* ctx) {
-    Scratch& s = ctx->sc;
-    const unsigned long long seq = ++s.pub_seq;
-    HIP_TRY(k_publish_counters(s.cnt, s.hcnt_dev, seq, ctx->stream));
-    return wait_publish(ctx, seq);
-}
-
-// Spin on the publish sequence number (a periodic stream query ends the spin on a failure).
-int wait_publish(tgo_ctx* ctx, unsigned long long seq) {
-    Scratch& s = ctx->sc;
-    const volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(s.hcnt) + kCounterWords;
-    for (uint64_t it = 1;; ++it) {
-        if (*flag == seq) break;
-        if ((it & 0x3FFF) == 0) {
-            const hipError_t q = hipStreamQuery(ctx->stream);
-            if (q != hipSuccess && q != hipErrorNotReady) return fail(ctx, TGO_E_HIP, hipGetErrorString(q));
-            if (q == hipSuccess && *flag != seq) return fail(ctx, TGO_E_HIP, "counter publish not visible after the stream drained");
-        }
-        __builtin_ia32_pause();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return TGO_OK;
-}
-
-// wait_publish for a publish that later ones may have overwritten: spin until the sequence
-// word reaches seq (the words then hold that publish or a later one).
-int wait_publish_at_least(tgo_ctx* ctx, unsigned long long seq) {
-    Scratch& s = ctx->sc;
-    const volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(s.hcnt) + kCounterWords;
-    for (uint64_t it = 1;; ++it) {
-        if (*flag >= seq) break;
-        if ((it & 0x3FFF) == 0) {
-            const hipError_t q = hipStreamQuery(ctx->stream);
-            if (q != hipSuccess && q != hipErrorNotReady) return fail(ctx, TGO_E_HIP, hipGetErrorString(q));
-            if (q == hipSuccess && *flag < seq) return fail(ctx, TGO_E_HIP, "loop state publish not visible after the stream drained");
-        }
-        __builtin_ia32_pause();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return TGO_OK;
-}
-
-// Exclusive scan of qdeg[0..qlen) into qpre[0..qlen] (qpre[qlen] = total).
-int scan_frontier(tgo_ctx* ctx, int64_t qlen) {
-    Scratch& s = ctx->sc;
-    HIP_TRY(hipMemsetAsync(s.qdeg + qlen, 0, sizeof(int64_t), ctx->stream));
-    HIP_TRY(scan_exclusive_i64(s.cub_tmp, s.cub_bytes, s.qdeg, s.qpre, qlen + 1, ctx->stream));
-    return TGO_OK;
-}
-
-// Direction-optimizing level loop for unit weights (Beamer et al., SC'12 heuristics).
-int run_bfs(tgo_ctx* ctx, int64_t seed, int max_depth, int scope) {
-    DevGraph& g = ctx->g;
-    Scratch& s = ctx->sc;
-    hipStream_t st = ctx->stream;
-    const int64_t n = g.n, words = (n + 63) / 64 + 1;
-    const View pull = pull_view(g, scope), push = push_view(g, scope);
-    HIP_TRY(k_fill_i32(s.level, -1, n, st));
-    HIP_TRY(hipMemsetAsync(s.vb, 0, words * 8, st));
-    HIP_TRY(hipMemsetAsync(s.fb, 0, words * 8, st));
-    int levels = 0;
-    if (seed >= 0) {
-        HIP_TRY(k_bfs_seed(push, s.level, s.vb, s.fb, s.q[0], s.qdeg, seed, st));
-        HIP_TRY(k_level_prep(s.cnt, s.nb, words, s.qdeg + 1, st));   // level 0: counters, nb, scan tail
-        int64_t qlen = 1;
-        int cur = 0;
-        bool bottom_up = false;
-        // Beamer's switch thresholds; TGO_BFS_ALPHA / TGO_BFS_BETA override for tuning.  Round 5:
-        // alpha 30 (bottom-up once the frontier's entries pass 1/30 of the unexplored ones) and
-        // beta 5000 (top-down again only below n/5000 frontier vertices), against Beamer's 15 / 18:
-        // hmean 301-318 -> 327-338 GTEPS over the 64 bench roots (profiles/r05ab_bfs_switch_ab.log).
-        // The roots that gain have a level-1 frontier of ~2300 hubs with ~18 M entries, just under
-        // mu / 15: top-down spent ~0.68 ms on that level, where the bottom-up finds nearly every
-        // vertex's parent among the hubs within a few entries.
-        static const double alpha = env_double("TGO_BFS_ALPHA", 30.0);
-        static const double beta = env_double("TGO_BFS_BETA", 5000.0);
-        static const bool trace = env_double("TGO_TRACE", 0.0) != 0.0;
-        // m_u: entries of unexplored vertices (push degrees); m_f: of the frontier.
-        const int64_t total_push = push.nlists > 1 ? (g.out.nnz + g.in.nnz)
-                                                   : (g.has_transpose ? g.push_t.nnz
-                                                                      : (scope == TGO_SCOPE_IN_E ? g.in.nnz : g.out.nnz));
-        int64_t mf = -1, mu = total_push;
-        bool queued = true;         // q[cur] holds the frontier (bottom-up levels only count it)
-        for (int L = 0; L < max_depth && qlen > 0; ++L) {
-            if (mf < 0) {   // degree of the seed, through the mapped counter page (a copy and a
-                            // stream synchronisation cost ~30 us before the first level)
-                const unsigned long long seq = ++s.pub_seq;
-                HIP_TRY(k_publish_words(s.qdeg, 1, s.hcnt_dev, seq, st));
-                if (int rc = wait_publish(ctx, seq)) return rc;
-                const int64_t d = static_cast<int64_t>(reinterpret_cast<volatile unsigned long long*>(s.hcnt)[0]);
-                mf = d;
-                mu -= d;
-            }
-            if (!bottom_up && static_cast<double>(mf) > static_cast<double>(mu) / alpha) bottom_up = true;
-            else if (bottom_up && static_cast<double>(qlen) < static_cast<double>(n) / beta) bottom_up = false;
-            // every level starts with zero counters, a clear nb and qdeg[qlen] = 0: level_turn
-            // at the end of the previous level (the first: the level_prep before the loop)
-            if (!bottom_up && !queued) {    // after bottom-up levels: queue the frontier bitmap
-                HIP_TRY(k_bfs_queue(push, g.n_active, s.fb, s.q[cur], s.qdeg, s.cnt, st));
-                HIP_TRY(k_level_prep(s.cnt, nullptr, 0, nullptr, st));   // the queue's counts out
-            }
-            queued = !bottom_up;
-            DevSpan span(st, "bfs.level", {"level", L}, {"bottom_up", bottom_up ? 1 : 0});
-            if (bottom_up) {
-                // words past n_active hold only entry-less vertices: nothing to find there
-                HIP_TRY(k_bu_step(pull, push, g.n_active, s.fb, s.vb, s.nb, s.level, s.cnt, L + 1, st));
-            } else {
-                HIP_TRY(scan_exclusive_i64(s.cub_tmp, s.cub_bytes, s.qdeg, s.qpre, qlen + 1, st));
-                // qdeg is reused for the next queue's degrees after the scan consumed it
-                HIP_TRY(k_td_expand(push, s.q[cur], s.qpre, qlen, s.level, s.vb, s.nb, s.q[cur ^ 1], s.qdeg, s.cnt, L + 1, st));
-            }
-            span.end();
-            // the counters to the host, then the next level's prep (fb, consumed, is its nb)
-            const unsigned long long seq = ++s.pub_seq;
-            HIP_TRY(k_level_turn(s.cnt, s.hcnt_dev, seq, s.fb, words, s.qdeg, st));
-            int rc = wait_publish(ctx, seq);
-            if (rc) return rc;
-            qlen = static_cast<int64_t>(s.hcnt->qlen);
-            mf = static_cast<int64_t>(s.hcnt->mf);
-            mu -= mf;
-            if (trace) std::fprintf(stderr, "[tgo] level %d %s -> next frontier %lld vertices, %lld entries (unexplored %lld)\n",
-                                    L, bottom_up ? "BU" : "TD", (long long)qlen, (long long)mf, (long long)mu);
-            std::swap(s.fb, s.nb);
-            cur ^= 1;
-            ++levels;
-        }
-    }
-    HIP_TRY(k_level_to_dist(s.level, s.dist, n, st));
-    trace_resolve(st);
-    ctx->st.levels = levels;
-    ctx->st.iterations = max_depth;   // the reference always runs iterations 0..maxDepth
-    return TGO_OK;
-}
-
-int run_sssp(tgo_ctx* ctx, int64_t seed, int max_depth, int scope, bool weighted) {
-    DevGraph& g = ctx->g;
-    Scratch& s = ctx->sc;
-    hipStream_t st = ctx->stream;
-    const int64_t n = g.n, words = (n + 63) / 64 + 1;
-    const View push = push_view(g, scope);
-    HIP_TRY(k_fill_i64(s.dist, INT64_MAX, n, st));
-    HIP_TRY(hipMemsetAsync(s.vb, 0, words * 8, st));
-    int levels = 0;
-    if (seed >= 0) {
-        HIP_TRY(k_sssp_seed(push, s.dist, s.msg, s.vb, s.q[0], s.qdeg, seed, st));
-        int64_t qlen = 1;
-        int cur = 0;
-        for (int L = 0; L < max_depth && qlen > 0; ++L) {
-            // counters, "improved this level" marks, scan tail
-            DevSpan span(st, "sssp.superstep", {"superstep", L}, {"queue", qlen});
-            HIP_TRY(k_level_prep(s.cnt, s.vb, words, s.qdeg + qlen, st));
-            HIP_TRY(scan_exclusive_i64(s.cub_tmp, s.cub_bytes, s.qdeg, s.qpre, qlen + 1, st));
-            int rc;
-            HIP_TRY(k_sssp_relax(push, s.q[cur], s.qpre, qlen, s.msg, s.dist, s.vb, s.q[cur ^ 1], s.qdeg, s.cnt, weighted ? 1 : 0, st));
-            span.end();
-            rc = read_counters(ctx);
-            if (rc) return rc;
-            if (s.hcnt->err) return fail(ctx, TGO_E_PROGRAM,
-                "vertex program failed: a traversed edge has no value for the weight property");
-            qlen = static_cast<int64_t>(s.hcnt->qlen);
-            // snapshot the improved vertices' distances: these are their messages
-            if (qlen > 0) HIP_TRY(k_sssp_commit(s.q[cur ^ 1], qlen, s.dist, s.msg, s.vb, st));
-            cur ^= 1;
-            ++levels;
-        }
-    }
-    HIP_TRY(k_dist_finalize(s.dist, n, st));
-    trace_resolve(st);
-    ctx->st.levels = levels;
-    ctx->st.iterations = max_depth;
-    return TGO_OK;
-}
-
-// Bucket width when the caller passes 0: TGO_DELTA, else a quarter of the mean edge weight
-// (RMAT scale 24, weights 1..255: 39 ms at width 32 against 49 ms at 256 and 43 ms at one
-// bucket per 2048 — profiles/r01_sssp_delta_sweep.log).
-int64_t default_delta(const DevGraph& g, bool weighted) {
-    const double env = env_double("TGO_DELTA", 0.0);
-    if (env > 0) return static_cast<int64_t>(env);
-    return std::max<int64_t>(1, static_cast<int64_t>(weighted ? 0.25 * g.mean_weight : 1.0));
-}
-
-// The light/heavy loop driven from the device (delta_loop.hip): the host enqueues steps in
-// batches and reads the loop state once per batch (dist, pending and member bitmaps are
-// initialised by the caller).
-int run_delta_device(tgo_ctx* ctx, int64_t seed, int64_t delta, bool force_scan) {
-    DevGraph& g = ctx->g;
-    Scratch& s = ctx->sc;
-    hipStream_t st = ctx->stream;
-    const int64_t n = g.n;
-    static const bool trace = env_double("TGO_TRACE", 0.0) != 0.0;
-    static const int batch = static_cast<int>(std::max(1.0, env_double("TGO_DS_BATCH", 8.0)));
-    // Piles (binned loop, TGO_DS_BINS=0 turns them off): a relaxation from bucket k reaches at
-    // most bucket k + 1 + (max_weight - 1) / delta, so that many + 1 piles in a ring hold every
-    // pending vertex; wider weight ranges keep the bitmap-scan loop.
-    static const bool bins_env = env_double("TGO_DS_BINS", 1.0) != 0.0;
-    const bool bins_on = ctx->ds_bins < 0 ? bins_env : ctx->ds_bins != 0;
-    const int64_t reach = 2 + (std::max<int64_t>(g.max_weight, 1) - 1) / delta;
-    const int nbins = (bins_on && !force_scan && reach <= kDsMaxBins) ? static_cast<int>(reach) : 0;
-    // TGO_DS_DONE=1: the relax skips the distance read of done targets (measured neutral at
-    // RMAT-24: the largest phases come before most vertices are done); TGO_DS_PILE_SCAN: piles
-    // above this fraction of n are extracted by the bitmap scan
-    static const bool done_env = env_double("TGO_DS_DONE", 0.0) != 0.0;
-    const bool done_filter = ctx->ds_done < 0 ? done_env : ctx->ds_done != 0;
-    static const double pile_scan = env_double("TGO_DS_PILE_SCAN", 1.0 / 16.0);
-    const int64_t scan_above = static_cast<int64_t>(pile_scan * static_cast<double>(n));
-    if (!s.ds_loop) {
-        for (int b = 0; b < 2; ++b) {
-            HIP_TRY(dev_alloc(ctx, s.ds_q[b], 2 * n + 2));
-            HIP_TRY(dev_alloc(ctx, s.ds_qp[b], 2 * n + 2));
-        }
-        HIP_TRY(dev_alloc(ctx, s.ds_loop, 1));
-        ctx->st.device_bytes = ctx->dev_bytes;
-    }
-    const int64_t cap = ctx->ds_pile_cap > 0 ? ctx->ds_pile_cap : std::max<int64_t>(n, 1024);
-    if (nbins && s.ds_pile && s.ds_pile_cap != cap) {
-        dev_free(ctx, s.ds_pile, kDsMaxBins * s.ds_pile_cap);
-        s.ds_pile_cap = 0;
-    }
-    if (nbins && !s.ds_pile) {
-        // a pile holds up to n appends per bucket (more drop to the bitmap scan of that bucket)
-        s.ds_pile_cap = cap;
-        HIP_TRY(dev_alloc(ctx, s.ds_pile, kDsMaxBins * s.ds_pile_cap));
-        if (!s.ds_mlist) HIP_TRY(dev_alloc(ctx, s.ds_mlist, n + 1));
-        if (!s.ds_done) HIP_TRY(dev_alloc(ctx, s.ds_done, (n + 63) / 64 + 1));
-        ctx->st.device_bytes = ctx->dev_bytes;
-    }
-    if (nbins) HIP_TRY(hipMemsetAsync(s.ds_done, 0, ((n + 63) / 64 + 1) * 8, st));
-    // Pull form (TGO_DS_PULL = members as a fraction of n, 0 = off): a finished bucket with at
-    // least that many members has its heavy entries pulled by the vertices that can still
-    // improve (delta_loop.hip ds_pull_heavy) instead of pushed entry by entry.
-    static const double pull_env = env_double("TGO_DS_PULL", 0.0);
-    const double pull_frac = ctx->ds_pull >= 0 ? ctx->ds_pull : pull_env;
-    DsPull pull{};
-    if (nbins && pull_frac > 0) {
-        const int64_t words = (n + 63) / 64 + 1;
-        for (int b = 0; b < 2; ++b) {
-            if (!s.ds_pm[b]) HIP_TRY(dev_alloc(ctx, s.ds_pm[b], words));
-            if (!s.ds_pl[b]) HIP_TRY(dev_alloc(ctx, s.ds_pl[b], n + 1));
-            HIP_TRY(hipMemsetAsync(s.ds_pm[b], 0, words * 8, st));
-            pull.pm[b] = s.ds_pm[b];
-            pull.pl[b] = s.ds_pl[b];
-        }
-        ctx->st.device_bytes = ctx->dev_bytes;
-        pull.view = pull_view(g, g.scope);
-        pull.n_active = g.n_active > 0 ? std::min<int64_t>(g.n_active, n) : n;
-        pull.min_members = std::max<int64_t>(1, static_cast<int64_t>(pull_frac * static_cast<double>(n)));
-    }
-    HIP_TRY(k_ds_loop_seed(g.push_ws, s.ds_light, s.dist, s.ds_q[0], s.ds_qp[0], s.ds_loop, seed, delta, st));
-    DsLoop h{};
-    int cur = 0;
-    // Small steps (TGO_TUNE_DS_SMALL / TGO_DS_SMALL, default off; delta_loop.hip ds_small_steps):
-    // the tiny steps run in one block inside one launch.  The binned loop without the done
-    // filter or pulls.  Off by default: 12.6 -> 13.8 ms per RMAT-24 source
-    // (profiles/r05ss1_sssp_small_ab.log) — a tiny step is a chain of dependent memory
-    // round trips either way, and one block pays them with fewer loads in flight.
-    static const bool small_env = env_double("TGO_DS_SMALL", 0.0) != 0.0;
-    const bool small_on = ctx->ds_small < 0 ? small_env : ctx->ds_small != 0;
-    const bool small = small_on && nbins && !done_filter && pull.min_members == 0;
-    // every step either relaxes a non-empty queue or extracts (at most one extraction in a row
-    // takes nothing); a run needs far fewer than 4n + 64 steps — the bound only stops a bug
-    const int64_t max_steps = 4 * n + 64;
-    // Pipelined stop checks (TGO_DS_PIPE, default on): each batch ends with a publish of the
-    // stop flags to host-mapped words, and the host checks batch k while batch k + 1 runs (a
-    // batch after the stop only runs steps that find nothing to do).  The stream no longer
-    // drains at every check: one SSSP run had ~12 drains of ~60 us (profiles/r04v_sssp_timeline.txt).
-    static const bool pipe = env_double("TGO_DS_PIPE", 1.0) != 0.0;
-    if (pipe) {
-        unsigned long long pending = 0;                       // publish to check next (0: none)
-        bool stop = false;
-        for (int64_t steps = 0; !stop;) {
-            DevSpan span(st, "sssp.delta_steps", {"first_step", steps}, {"steps", batch});
-            for (int k = 0; k < batch; ++k) {
-                if (small)
-                    HIP_TRY(k_ds_loop_step_small(g.push_ws, s.ds_light, s.vb, s.ds_member, n, s.dist, s.msg, s.ds_q,
-                                                 s.ds_qp, s.ds_loop, delta, nbins, s.ds_pile, s.ds_pile_cap,
-                                                 s.ds_mlist, s.ds_done, scan_above, st));
-                else if (nbins)
-                    HIP_TRY(k_ds_loop_step_bins(g.push_ws, s.ds_light, s.vb, s.ds_member, n, s.dist, s.msg, s.ds_q,
-                                                s.ds_qp, s.ds_loop, cur, delta, nbins, s.ds_pile, s.ds_pile_cap,
-                                                s.ds_mlist, s.ds_done, done_filter, scan_above, pull, st));
-                else
-                    HIP_TRY(k_ds_loop_step(g.push_ws, s.ds_light, s.vb, s.ds_member, n, s.dist, s.msg, s.ds_q, s.ds_qp,
-                                           s.ds_loop, cur, delta, st));
-                cur ^= 1;
-            }
-            steps += batch;
-            span.end();
-            const unsigned long long seq = ++s.pub_seq;
-            HIP_TRY(k_ds_publish(s.ds_loop, s.hcnt_dev, seq, st));
-            if (pending) {
-                if (int rc = wait_publish_at_least(ctx, pending)) return rc;
-                const volatile unsigned long long* hw = reinterpret_cast<volatile unsigned long long*>(s.hcnt);
-                if (hw[1]) return fail(ctx, TGO_E_PROGRAM, "vertex program failed: a traversed edge has no value for the weight property");
-                stop = hw[0] != 0 || hw[2] != 0;
-            }
-            pending = seq;
-            if (!stop && steps > max_steps) return fail(ctx, TGO_E_HIP, "delta-stepping: the device loop did not converge");
-        }
-        HIP_TRY(hipMemcpyAsync(&h, s.ds_loop, sizeof(DsLoop), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (h.err) return fail(ctx, TGO_E_PROGRAM, "vertex program failed: a traversed edge has no value for the weight property");
-    }
-    for (int64_t steps = 0; !pipe;) {
-        DevSpan span(st, "sssp.delta_steps", {"first_step", steps}, {"steps", batch});
-        for (int k = 0; k < batch; ++k) {
-            if (small)
-                HIP_TRY(k_ds_loop_step_small(g.push_ws, s.ds_light, s.vb, s.ds_member, n, s.dist, s.msg, s.ds_q,
-                                             s.ds_qp, s.ds_loop, delta, nbins, s.ds_pile, s.ds_pile_cap, s.ds_mlist,
-                                             s.ds_done, scan_above, st));
-            else if (nbins)
-                HIP_TRY(k_ds_loop_step_bins(g.push_ws, s.ds_light, s.vb, s.ds_member, n, s.dist, s.msg, s.ds_q, s.ds_qp,
-                                            s.ds_loop, cur, delta, nbins, s.ds_pile, s.ds_pile_cap, s.ds_mlist,
-                                            s.ds_done, done_filter, scan_above, pull, st));
-            else
-                HIP_TRY(k_ds_loop_step(g.push_ws, s.ds_light, s.vb, s.ds_member, n, s.dist, s.msg, s.ds_q, s.ds_qp,
-                                       s.ds_loop, cur, delta, st));
-            cur ^= 1;
-        }
-        steps += batch;
-        span.end();
-        HIP_TRY(hipMemcpyAsync(&h, s.ds_loop, sizeof(DsLoop), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (h.err) return fail(ctx, TGO_E_PROGRAM, "vertex program failed: a traversed edge has no value for the weight property");
-        if (h.spill) break;
-        if (h.done) break;
-        if (steps > max_steps) return fail(ctx, TGO_E_HIP, "delta-stepping: the device loop did not converge");
-    }
-    if (h.spill) {
-        // a relaxation reached past the piles (the weight bound was wrong): start again with
-        // the bitmap-scan loop (dist, pending and member state re-initialised by the caller)
-        trace_resolve(st);
-        return TGO_E_STATE;
-    }
-    HIP_TRY(k_dist_finalize(s.dist, n, st));
-    trace_resolve(st);
-    if (trace)
-        std::fprintf(stderr, "[tgo] delta %lld (device loop, %d piles): %llu phases, %llu buckets, %llu extractions "
-                     "(%llu bitmap scans), %llu entries relaxed\n", (long long)delta, nbins, h.phases, h.buckets,
-                     h.extractions, h.full_scans, h.relaxed);
-    ctx->st.levels = static_cast<int32_t>(h.phases);
-    ctx->st.relaxed_entries = static_cast<int64_t>(h.relaxed);
-    return TGO_OK;
-}
-
-// Light/heavy delta-stepping (delta.hip, weighted one-GPU loads): a bucket's phases relax
-// light entries only; when its near queue runs dry the bucket's members relax their heavy
-// entries once; then the threshold moves to the next non-empty bucket.
-int run_delta_split(tgo_ctx* ctx, int64_t seed, int64_t delta) {
-    DevGraph& g = ctx->g;
-    Scratch& s = ctx->sc;
-    hipStream_t st = ctx->stream;
-    const int64_t n = g.n, words = (n + 63) / 64 + 1;
-    static const bool trace = env_double("TGO_TRACE", 0.0) != 0.0;
-    if (!s.ds_light) {
-        HIP_TRY(dev_alloc(ctx, s.ds_light, n + 1));
-        HIP_TRY(dev_alloc(ctx, s.ds_member, words));
-        ctx->st.device_bytes = ctx->dev_bytes;
-    }
-    if (s.ds_light_delta != delta) {
-        HIP_TRY(k_ds_light_end(g.push_ws, delta, n, s.ds_light, st));
-        s.ds_light_delta = delta;
-    }
-    HIP_TRY(k_fill_i64(s.dist, INT64_MAX, n, st));
-    HIP_TRY(hipMemsetAsync(s.vb, 0, words * 8, st));        // pending bitmap
-    HIP_TRY(hipMemsetAsync(s.ds_member, 0, words * 8, st));
-    // device-driven steps (delta_loop.hip) unless TGO_DS_HOSTLOOP=1 or the packed queue
-    // counters could overflow: a queue holds up to 2n + 2 takes (a light and a heavy take per
-    // vertex, ds_q / ds_qp are sized for that) in the count field above kDsCountShift, and up
-    // to nnz entries below it
-    static const bool host_loop = env_double("TGO_DS_HOSTLOOP", 0.0) != 0.0;
-    constexpr int64_t kDsMaxCount = int64_t(1) << (64 - kDsCountShift);
-    static_assert(kDsCountShift > 32 && kDsCountShift < 64, "queue counter layout");
-    if (!host_loop && seed >= 0 && 2 * n + 2 < kDsMaxCount && g.push_ws.nnz < (int64_t(1) << kDsCountShift)) {
-        const int rc = run_delta_device(ctx, seed, delta, false);
-        if (rc != TGO_E_STATE) return rc;
-        HIP_TRY(k_fill_i64(s.dist, INT64_MAX, n, st));
-        HIP_TRY(hipMemsetAsync(s.vb, 0, words * 8, st));
-        HIP_TRY(hipMemsetAsync(s.ds_member, 0, words * 8, st));
-        return run_delta_device(ctx, seed, delta, true);
-    }
-    int phases = 0, buckets = 0;
-    int64_t relaxed = 0;
-    // TGO_DS_TRACE=1: one line per phase (queue, entries, wall time since the previous phase)
-    static const bool phase_trace = env_double("TGO_DS_TRACE", 0.0) != 0.0;
-    auto t_phase = std::chrono::steady_clock::now();
-    if (seed >= 0) {
-        HIP_TRY(k_ds_seed_ws(g.push_ws, s.ds_light, s.dist, s.q[0], s.qdeg, seed, st));
-        int64_t qlen = 1, thr = delta;
-        int cur = 0;
-        for (;;) {
-            if (qlen == 0) {
-                // bucket settled: next near queue + the members' heavy entries, one extraction
-                HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), st));
-                HIP_TRY(hipMemsetAsync(&s.cnt->red[0], 0x7F, sizeof(unsigned long long), st));   // ~INT64_MAX
-                HIP_TRY(k_ds_pending_min_ws(s.vb, s.ds_member, words, s.dist, s.cnt, st));
-                if (int rc = read_counters(ctx)) return rc;
-                const int64_t pending = static_cast<int64_t>(s.hcnt->red[1]);
-                const int64_t members = static_cast<int64_t>(s.hcnt->red2);
-                if (pending == 0 && members == 0) break;        // converged
-                if (pending > 0) {
-                    const int64_t mn = static_cast<int64_t>(s.hcnt->red[0]);
-                    if (mn >= thr) thr = (mn / delta + 1) * delta;
-                    ++buckets;
-                }
-                HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), st));
-                HIP_TRY(k_ds_extract_ws(g.push_ws, s.ds_light, s.vb, s.ds_member, n, s.dist, thr, s.q[cur], s.qdeg, s.cnt,
-                                        st));
-                if (int rc = read_counters(ctx)) return rc;
-                qlen = static_cast<int64_t>(s.hcnt->qlen);
-                if (trace) std::fprintf(stderr, "[tgo] delta bucket thr %lld: %lld pending, %lld members, %lld queued\n",
-                                        (long long)thr, (long long)pending, (long long)members, (long long)qlen);
-                if (qlen == 0) {
-                    if (pending > 0) return fail(ctx, TGO_E_HIP, "delta-stepping: extraction found no vertex below the threshold");
-                    continue;                                   // members without heavy entries
-                }
-            }
-            HIP_TRY(k_ds_commit_ws(s.q[cur], qlen, s.dist, s.msg, s.vb, s.ds_member, s.qdeg, s.cnt, st));
-            HIP_TRY(scan_exclusive_i64(s.cub_tmp, s.cub_bytes, s.qdeg, s.qpre, qlen + 1, st));   // tail zeroed by commit
-            HIP_TRY(k_ds_relax_ws(g.push_ws, s.ds_light, s.q[cur], s.qpre, qlen, s.msg, s.dist, s.vb, s.q[cur ^ 1], s.qdeg,
-                                  s.cnt, thr, st));
-            if (int rc = read_counters(ctx)) return rc;
-            if (s.hcnt->err) return fail(ctx, TGO_E_PROGRAM,
-                "vertex program failed: a traversed edge has no value for the weight property");
-            relaxed += static_cast<int64_t>(s.hcnt->red[1]);
-            if (phase_trace) {
-                const auto now = std::chrono::steady_clock::now();
-                std::fprintf(stderr, "[tgo] ds phase %d thr %lld: queue %lld, entries %llu, next %llu, %.1f us\n", phases,
-                             (long long)thr, (long long)qlen, s.hcnt->red[1], s.hcnt->qlen,
-                             std::chrono::duration<double, std::micro>(now - t_phase).count());
-                t_phase = now;
-            }
-            qlen = static_cast<int64_t>(s.hcnt->qlen);
-            cur ^= 1;
-            ++phases;
-        }
-    }
-    HIP_TRY(k_dist_finalize(s.dist, n, st));
-    if (trace) std::fprintf(stderr, "[tgo] delta %lld (light/heavy): %d phases, %d buckets, %lld entries relaxed\n",
-                            (long long)delta, phases, buckets, (long long)relaxed);
-    ctx->st.levels = phases;
-    ctx->st.relaxed_entries = relaxed;
-    return TGO_OK;
-}
-
-// Delta-stepping (delta.hip): converged distances, near queue relaxed phase by phase,
-// bucket threshold advanced from the minimum pending distance when the queue runs dry.
-int run_delta(tgo_ctx* ctx, int64_t seed, int scope, bool weighted, int64_t delta) {
-    DevGraph& g = ctx->g;
-    Scratch& s = ctx->sc;
-    hipStream_t st = ctx->stream;
-    const int64_t n = g.n, words = (n + 63) / 64 + 1;
-    const View push = push_view(g, scope);
-    static const bool trace = env_double("TGO_TRACE", 0.0) != 0.0;
-    if (delta <= 0) delta = default_delta(g, weighted);
-    if (weighted && g.push_ws_ready && scope == g.scope) return run_delta_split(ctx, seed, delta);
-    HIP_TRY(k_fill_i64(s.dist, INT64_MAX, n, st));
-    HIP_TRY(hipMemsetAsync(s.vb, 0, words * 8, st));        // pending bitmap
-    int phases = 0, buckets = 0;
-    int64_t relaxed = 0;
-    if (seed >= 0) {
-        HIP_TRY(k_ds_seed(push, s.dist, s.q[0], s.qdeg, seed, st));
-        int64_t qlen = 1, thr = delta;
-        int cur = 0;
-        for (;;) {
-            if (qlen == 0) {
-                HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), st));
-                HIP_TRY(hipMemsetAsync(&s.cnt->red[0], 0x7F, sizeof(unsigned long long), st));   // ~INT64_MAX
-                HIP_TRY(k_ds_pending_min(s.vb, words, s.dist, s.cnt, st));
-                if (int rc = read_counters(ctx)) return rc;
-                if (s.hcnt->red[1] == 0) break;                 // nothing pending: converged
-                const int64_t mn = static_cast<int64_t>(s.hcnt->red[0]);
-                if (mn >= thr) thr = (mn / delta + 1) * delta;
-                ++buckets;
-                HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), st));
-                HIP_TRY(k_ds_extract(push, s.vb, n, s.dist, thr, s.q[cur], s.qdeg, s.cnt, st));
-                if (int rc = read_counters(ctx)) return rc;
-                qlen = static_cast<int64_t>(s.hcnt->qlen);
-                if (trace) std::fprintf(stderr, "[tgo] delta bucket thr %lld: min pending %lld, %llu pending, %lld queued\n",
-                                        (long long)thr, (long long)mn, s.hcnt->red[1], (long long)qlen);
-                if (qlen == 0) return fail(ctx, TGO_E_HIP, "delta-stepping: extraction found no vertex below the threshold");
-            }
-            HIP_TRY(k_ds_commit(s.q[cur], qlen, s.dist, s.msg, s.vb, st));
-            if (int rc = scan_frontier(ctx, qlen)) return rc;
-            HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), st));
-            HIP_TRY(k_ds_relax(push, s.q[cur], s.qpre, qlen, s.msg, s.dist, s.vb, s.q[cur ^ 1], s.qdeg, s.cnt,
-                               weighted ? 1 : 0, thr, st));
-            if (int rc = read_counters(ctx)) return rc;
-            if (s.hcnt->err) return fail(ctx, TGO_E_PROGRAM,
-                "vertex program failed: a traversed edge has no value for the weight property");
-            relaxed += static_cast<int64_t>(s.hcnt->red[1]);      // qpre[qlen], set by ds_relax
-            qlen = static_cast<int64_t>(s.hcnt->qlen);
-            cur ^= 1;
-            ++phases;
-        }
-    }
-    HIP_TRY(k_dist_finalize(s.dist, n, st));
-    if (trace) std::fprintf(stderr, "[tgo] delta %lld: %d phases, %d buckets, %lld entries relaxed\n",
-                            (long long)delta, phases, buckets, (long long)relaxed);
-    ctx->st.levels = phases;
-    ctx->st.relaxed_entries = relaxed;
-    return TGO_OK;
-}
-
-int finish_distance_program(tgo_ctx* ctx, int scope, int flags, int64_t* dist_out) {
-    Scratch& s = ctx->sc;
-    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_TRY(hipEventSynchronize(ctx->ev1));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->st.last_kernel_ms = ms;
-    if (flags & TGO_FLAG_STATS) {
-        // reached vertices and the entries of their pull lists (both lists for bothE)
-        HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), ctx->stream));
-        HIP_TRY(k_reach_stats(pull_view(ctx->g, scope), s.dist, ctx->g.n, s.cnt->red, ctx->stream));
-        int rc = read_counters(ctx);
-        if (rc) return rc;
-        ctx->st.reached = static_cast<int64_t>(s.hcnt->red[0]);
-        ctx->st.reached_entries = static_cast<int64_t>(s.hcnt->red[1]);
-    }
-    if (dist_out) {
-        HIP_TRY(k_unpermute_i64(s.dist, ctx->g.perm, s.msg, ctx->g.n, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(dist_out, s.msg, ctx->g.n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-    }
-    (void)scope;
-    return TGO_OK;
-}
-
 }  // namespace
 
 // ============================================================================ C-ABI
-
-namespace tgo { double ms_split_of(const tgo_ctx* ctx); double ms_stay_of(const tgo_ctx* ctx); double ms_sparse_of(const tgo_ctx* ctx); int64_t ms_head_of(const tgo_ctx* ctx); int part_upload(tgo_ctx* ctx, HostGraph& h, int64_t n_global, int64_t lo); }
 
 namespace {
 struct TrimTemps {                  // tmp_cache.cpp: nothing stays reserved between loads
@@ -1425,10 +745,7 @@ int tgo_load_rows(tgo_ctx* ctx, const tgo_rows* rows, const tgo_schema* schema, 
     std::string err;
     // device decode (decode.hip) unless TGO_HOST_DECODE=1 picks the multi-threaded host decoder
     // (latched at the first batch of a load, so one load never mixes the two)
-    if (!ctx->staging.active) {
-        const char* host = std::getenv("TGO_HOST_DECODE");
-        ctx->host_decode = host && std::atoi(host) != 0;
-    }
+    if (!ctx->staging.active) ctx->host_decode = env_i64("TGO_HOST_DECODE", 0) != 0;
     int rc = ctx->host_decode ? decode_rows(ctx->staging, rows, schema, opts, ctx->opts.partition_bits,
                                        ctx->opts.hard_query_limit, threads_of(ctx), err)
                          : stage_rows_raw(ctx->staging, rows, schema, opts, ctx->dec, ctx->stream, err);
@@ -1448,12 +765,12 @@ int tgo_finish_load(tgo_ctx* ctx) {
     std::string err;
     // the staged work blocks, decoded in one device pass (decode.hip); the kept entries stay
     // on the device for the device assembly
-    const bool dev_asm = env_i64("TGO_HOST_ASSEMBLY", 0) == 0;
+    const bool dev_asm = !host_assembly();
     int rc = decode_staged_raw(ctx->staging, ctx->opts.partition_bits, ctx->opts.hard_query_limit, ctx->dec,
                                ctx->stream, err, dev_asm);
     ctx->dec.release();
     if (rc) { ctx->staging = RowStaging(); return fail(ctx, rc, err); }
-    if (env_i64("TGO_TRACE", 0))
+    if (trace_on())
         std::fprintf(stderr, "[tgo] finish_load decode %8.1f ms\n",
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     // CSR assembly on the device (assemble.hip) unless TGO_HOST_ASSEMBLY=1 or the scan holds
@@ -1472,7 +789,7 @@ int tgo_finish_load(tgo_ctx* ctx) {
     if (rc) { ctx->staging = RowStaging(); return fail(ctx, rc, err); }
     h.wval = std::move(wval);
     h.d_wval = std::move(d_wval);
-    if (env_i64("TGO_TRACE", 0))
+    if (trace_on())
         std::fprintf(stderr, "[tgo] finish_load decode + assembly (%s) %8.1f ms\n", on_dev ? "device" : "host",
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     free_graph(ctx);
@@ -1494,11 +811,11 @@ int tgo_load_edges(tgo_ctx* ctx, const tgo_edges* edges, const tgo_load_opts* op
     HostGraph h;
     std::string err;
     // device assembly (assemble.hip) unless TGO_HOST_ASSEMBLY=1
-    const bool on_dev = env_i64("TGO_HOST_ASSEMBLY", 0) == 0;
+    const bool on_dev = !host_assembly();
     int rc = on_dev ? assemble_edges_device(edges, opts, ctx->opts.hard_query_limit, h, ctx->stream, err)
                     : assemble_from_edges(edges, opts, ctx->opts.hard_query_limit, h, threads_of(ctx), err);
     if (rc) return fail(ctx, rc, err);
-    if (env_i64("TGO_TRACE", 0))
+    if (trace_on())
         std::fprintf(stderr, "[tgo] load_edges assembly (%s) %8.1f ms\n", on_dev ? "device" : "host",
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     free_graph(ctx);
@@ -1534,7 +851,7 @@ int tgo_load_csr(tgo_ctx* ctx, int64_t n, const int64_t* titan_ids, const int64_
     int rc = stage_csr_device(in, weighted, st, ctx->stream, err);
     if (rc) return fail(ctx, rc, err);
     HostGraph h;
-    const bool on_dev = env_i64("TGO_HOST_ASSEMBLY", 0) == 0;
+    const bool on_dev = !host_assembly();
     if (!on_dev) rc = staging_entries_to_host(st, ctx->stream, err);
     if (!rc) rc = on_dev ? assemble_rows_device(st, h, ctx->stream, err) : assemble_from_rows(st, h, threads_of(ctx), err);
     if (rc) return fail(ctx, rc, err);
@@ -1574,497 +891,6 @@ int tgo_graph_perm(tgo_ctx* ctx, int32_t* perm) {
     if (!ctx->loaded) return fail(ctx, TGO_E_STATE, "no graph loaded");
     (void)hipSetDevice(ctx->opts.device);
     HIP_TRY(hipMemcpy(perm, ctx->g.perm, ctx->g.n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return TGO_OK;
-}
-
-int tgo_bfs(tgo_ctx* ctx, const tgo_bfs_args* a, int64_t* dist_out) {
-    if (!ctx) return TGO_E_INVALID;
-    ctx->res_kind = -1;
-    if (!a) return fail(ctx, TGO_E_INVALID, "null args");
-    int rc = check_program(ctx, a->scope);
-    if (rc) return rc;
-    if (a->max_depth < 0) return fail(ctx, TGO_E_INVALID, "max_depth < 0");
-    (void)hipSetDevice(ctx->opts.device);
-    int64_t seed;
-    if ((rc = resolve_seed(ctx, a->seed, a->seed_is_dense, seed))) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    if ((rc = run_bfs(ctx, seed, a->max_depth, a->scope))) return rc;
-    if ((rc = finish_distance_program(ctx, a->scope, a->flags, dist_out))) return rc;
-    ctx->res_kind = TGO_RESULT_DISTANCE;
-    ctx->res_empty = false;
-    ctx->res_src = ResultSource{ctx->sc.dist, nullptr};
-    return TGO_OK;
-}
-
-int tgo_sssp(tgo_ctx* ctx, const tgo_sssp_args* a, int64_t* dist_out) {
-    if (!ctx) return TGO_E_INVALID;
-    ctx->res_kind = -1;
-    if (!a) return fail(ctx, TGO_E_INVALID, "null args");
-    int rc = check_program(ctx, a->scope);
-    if (rc) return rc;
-    if (a->max_depth < 0) return fail(ctx, TGO_E_INVALID, "max_depth < 0");
-    if (a->mode != TGO_SSSP_HOP_BOUNDED && a->mode != TGO_SSSP_DELTA) return fail(ctx, TGO_E_INVALID, "invalid mode");
-    if (ctx->g.has_weight && ctx->g.weight_dt != TGO_DT_INTEGER)
-        return fail(ctx, TGO_E_UNSUPPORTED, "ShortestDistanceVertexProgram reads edge.<Integer>value(weight): the weight "
-                                            "property is not an Integer key (ClassCastException in the reference)");
-    (void)hipSetDevice(ctx->opts.device);
-    int64_t seed;
-    if ((rc = resolve_seed(ctx, a->seed, a->seed_is_dense, seed))) return rc;
-    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    ctx->st.relaxed_entries = 0;
-    if (a->mode == TGO_SSSP_DELTA) {
-        // converged distances (== the reference's whenever maxDepth >= the hop count of
-        // every shortest path); max_depth only sets the reported iteration count
-        if (ctx->g.has_weight && ctx->g.min_weight < 0)
-            return fail(ctx, TGO_E_INVALID, "DELTA mode needs non-negative weights");
-        if ((rc = run_delta(ctx, seed, a->scope, ctx->g.has_weight, a->delta))) return rc;
-        ctx->st.iterations = a->max_depth;
-    } else {
-        if ((rc = run_sssp(ctx, seed, a->max_depth, a->scope, ctx->g.has_weight))) return rc;
-    }
-    if ((rc = finish_distance_program(ctx, a->scope, a->flags, dist_out))) return rc;
-    ctx->res_kind = TGO_RESULT_DISTANCE;
-    ctx->res_empty = false;
-    ctx->res_src = ResultSource{ctx->sc.dist, nullptr};
-    return TGO_OK;
-}
-
-// ------------------------------------------------------------------ multi-source BFS
-static LevelPlanes ms_planes(tgo_ctx* ctx) { return LevelPlanes{ctx->sc.ms_lvl, ctx->g.n}; }
-
-// Zero the level planes a discovery at `level` writes (planes 0..floor(log2(level))) that
-// this sweep has not zeroed yet: vertices reached earlier have levels < 2^k, whose bit k
-// is 0, so a plane is valid from the moment it is zeroed.
-static int ms_planes_for(tgo_ctx* ctx, int32_t level) {
-    Scratch& s = ctx->sc;
-    while (s.ms_nplanes < kLevelPlanes && (level >> s.ms_nplanes) != 0) {
-        HIP_TRY(hipMemsetAsync(s.ms_lvl + static_cast<int64_t>(s.ms_nplanes) * ctx->g.n, 0,
-                               ctx->g.n * sizeof(uint64_t), ctx->stream));
-        ++s.ms_nplanes;
-    }
-    return TGO_OK;
-}
-
-static int ms_alloc(tgo_ctx* ctx) {
-    Scratch& s = ctx->sc;
-    if (s.ms_vis) return TGO_OK;
-    const int64_t n = ctx->g.n;
-    HIP_TRY(dev_alloc(ctx, s.ms_vis, n + 1));
-    HIP_TRY(dev_alloc(ctx, s.ms_fr, n + 1));
-    HIP_TRY(dev_alloc(ctx, s.ms_nx, n + 1));
-    HIP_TRY(dev_alloc(ctx, s.ms_lvl, n * kLevelPlanes + 1));
-    HIP_TRY(dev_alloc(ctx, s.ms_fbm, (n + 63) / 64 + 1));
-    HIP_TRY(dev_alloc(ctx, s.ms_seeds, TGO_MAX_SOURCES));
-    HIP_TRY(dev_alloc(ctx, s.ms_stat, 2 * TGO_MAX_SOURCES));
-    HIP_TRY(dev_alloc(ctx, s.ms_srcent, TGO_MAX_SOURCES));
-    ctx->st.device_bytes = ctx->dev_bytes;
-    return TGO_OK;
-}
-
-// The cold layout of the scope's pull view for the split first pull level (built once per
-// graph and scope, on first use): neighbours >= hot (TGO_MS_COLD_HOT, 384 K = 3 MB of masks,
-// the hot head every XCD's L2 keeps) in segments of TGO_MS_COLD_SEG (384 K) neighbours.
-static int ms_cold_layout(tgo_ctx* ctx, int32_t scope, const View& pull, int64_t hot_req) {
-    DevGraph& g = ctx->g;
-    Scratch& s = ctx->sc;
-    static const int64_t hot_env = static_cast<int64_t>(env_double("TGO_MS_COLD_HOT", 393216.0));
-    static const int64_t seg_env = static_cast<int64_t>(env_double("TGO_MS_COLD_SEG", 393216.0));
-    const int64_t hot = hot_req > 1 ? hot_req : hot_env, seg = hot_req > 1 ? hot_req : seg_env;
-    if (g.msc_scope == scope && g.msc_req == hot) return TGO_OK;
-    g.msc_scope = scope;
-    g.msc_req = hot;
-    g.msc_C = 0;
-    if (hot <= 0 || hot >= INT32_MAX || seg <= 0) return TGO_OK;
-    Span span("msbfs.cold_layout");
-    DevArray<int32_t> cadj, crow;
-    int64_t C = 0;
-    std::string err;
-    if (int rc = build_ms_cold(pull, g.n, static_cast<int32_t>(hot), seg, cadj, crow, C, ctx->stream, err))
-        return fail(ctx, rc, err);
-    if (C == 0) return TGO_OK;
-    adopt(ctx, g.msc_adj, cadj);
-    adopt(ctx, g.msc_row, crow);
-    if (!s.ms_cacc) {
-        HIP_TRY(dev_alloc(ctx, s.ms_cacc, g.n + 1));
-        HIP_TRY(dev_alloc(ctx, s.ms_need, g.n + 1));
-        HIP_TRY(hipMemsetAsync(s.ms_need, 0, g.n + 1, ctx->stream));
-    }
-    g.msc_C = C;
-    g.msc_hot = static_cast<int32_t>(hot);
-    ctx->st.device_bytes = ctx->dev_bytes;
-    return TGO_OK;
-}
-
-int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_bfs_args* a, int64_t* dist_out) {
-    if (!ctx) return TGO_E_INVALID;
-    ctx->res_kind = -1;
-    if (!a || !seeds) return fail(ctx, TGO_E_INVALID, "null args");
-    if (nseeds < 1 || nseeds > TGO_MAX_SOURCES) return fail(ctx, TGO_E_INVALID, "nseeds must be in [1, 64]");
-    int rc = check_program(ctx, a->scope);
-    if (rc) return rc;
-    if (a->max_depth < 0) return fail(ctx, TGO_E_INVALID, "max_depth < 0");
-    (void)hipSetDevice(ctx->opts.device);
-    if ((rc = ms_alloc(ctx))) return rc;
-    DevGraph& g = ctx->g;
-    Scratch& s = ctx->sc;
-    hipStream_t st = ctx->stream;
-    const int64_t n = g.n;
-    const View pull = pull_view(g, a->scope), push = push_view(g, a->scope);
-    std::vector<int64_t> in(nseeds);
-    std::vector<int32_t> uniq;
-    for (int r = 0; r < nseeds; ++r) {
-        if ((rc = resolve_seed(ctx, seeds[r], a->seed_is_dense, in[r]))) return rc;
-        if (in[r] < 0) return fail(ctx, TGO_E_INVALID, "multi-source BFS needs seeds that are executed vertices");
-        if (std::find(uniq.begin(), uniq.end(), static_cast<int32_t>(in[r])) == uniq.end())
-            uniq.push_back(static_cast<int32_t>(in[r]));
-    }
-    s.ms_nsrc = nseeds;
-    HIP_TRY(hipEventRecord(ctx->ev0, st));
-    HIP_TRY(hipMemcpyAsync(s.ms_seeds, in.data(), nseeds * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s.q[0], uniq.data(), uniq.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(s.ms_vis, 0, n * 8, st));
-    // both mask buffers are still zero when the last sweep ended on an empty sparse level; the
-    // flag is down while a sweep runs, so a failed or depth-cut sweep leaves it down
-    const bool masks_zero = s.ms_masks_zero;
-    s.ms_masks_zero = false;
-    if (!masks_zero) HIP_TRY(hipMemsetAsync(s.ms_fr, 0, n * 8, st));
-    s.ms_nplanes = 0;
-    HIP_TRY(k_ms_seed(s.ms_seeds, nseeds, s.ms_vis, s.ms_fr, INT64_MAX, st));
-    HIP_TRY(k_degree_i64(push, s.q[0], static_cast<int64_t>(uniq.size()), s.qdeg, st));
-    const uint64_t full = nseeds == 64 ? ~0ULL : ((1ULL << nseeds) - 1ULL);
-    const int64_t total = pull.nlists > 1 ? g.out.nnz + g.in.nnz : (a->scope == TGO_SCOPE_IN_E ? g.out.nnz : g.in.nnz);
-    static const double ms_alpha = env_double("TGO_MS_ALPHA", 12.0);
-    static const bool trace = env_double("TGO_TRACE", 0.0) != 0.0;
-    // frontier-bitmap filter of pull levels: measured slower (every pull level: 3.07 -> 3.99 ms,
-    // 0.95 -> 1.25, 0.18 -> 0.19; MS-BFS 3146 -> 2471 GTEPS, profiles/r02ad_*): the mask gathers
-    // mostly hit L2 / the Infinity Cache already and the probe adds a dependent load.  Opt-in.
-    // TGO_MS_FILTER_FROM=H probes the bitmap only for neighbours >= H (the cold ids whose
-    // gathers miss L2); TGO_MS_FILTER=1 is H=0, the filter for every neighbour.  Measured on
-    // RMAT-24 (profiles/r03h_ms_filter.log): off 5.59 ms/sweep; H = 0 7.05, 128K 6.32, 256K 6.10,
-    // 384K 5.93, 1M 5.62 — monotone towards no filter, so the probe's dependent load costs more
-    // than the cold gathers it saves.  Off by default.
-    static const int32_t filter_from = env_double("TGO_MS_FILTER", 0.0) != 0.0
-        ? 0 : static_cast<int32_t>(env_double("TGO_MS_FILTER_FROM", -1.0));
-    const bool filter = filter_from >= 0 && filter_from < n;
-    // TGO_MS_SPLIT: push budget of the pull levels' sparse sources, as a fraction of the
-    // list entries (0 = every source pulled)
-    const double split_frac = tgo::ms_split_of(ctx);
-    // TGO_TUNE_MS_STAY (gamma): after a pull level the next one pulls too while the list entries
-    // of the still-open vertices (mu, what a pull walks at most) are <= gamma x the frontier's
-    // entries (mf, what a push ORs atomically) — both directions pay one pass over the masks
-    // (the pull itself / ms_queue).  TGO_TUNE_MS_SPARSE: a push level whose frontier is queued
-    // and has at most that fraction of n_active entries (level 0 always) runs in the sparse
-    // form (k_ms_push_sparse / k_ms_settle_sparse): no pass over every mask.
-    const double stay_gamma = tgo::ms_stay_of(ctx), sparse_frac = tgo::ms_sparse_of(ctx);
-    // TGO_TUNE_MS_HEAD: the entries of its own lists a lane with a long list probes before the
-    // whole wave takes the list (0 = off)
-    const int64_t head = tgo::ms_head_of(ctx);
-    int64_t qlen = static_cast<int64_t>(uniq.size());
-    int64_t mf = 0;             // the seeds' entries are not read back: level 0 always pushes (a
-                                // direction is policy only; the read cost a stream drain, ~45 us)
-    int64_t reached = qlen;     // vertices reached by any source so far
-    bool srcent_ready = false;  // ms_srcent holds the current frontier's push entries per source
-    static const double push_light = env_double("TGO_MS_PUSH_LIGHT", 1.0 / 16.0);
-    static const bool push_probe = env_double("TGO_MS_PUSH_PROBE", 1.0) != 0.0;
-    // measured slower at RMAT-24 (second level 446 -> 561 us, profiles/r04t_ms_push_ab.log): off
-    static const int push_range_log2 = static_cast<int>(env_double("TGO_MS_PUSH_RANGE", 0.0));
-    static const int64_t push_range_min = static_cast<int64_t>(env_double("TGO_MS_PUSH_RANGE_MIN", 1048576.0));
-    const int depth = std::min(a->max_depth, 65534);
-    uint64_t* fr = s.ms_fr;
-    uint64_t* nx = s.ms_nx;
-    int cur = 0, levels = 0;
-    bool queued = true;         // q[cur] holds the frontier (pull levels only count it)
-    bool pulled = false;        // the previous level pulled
-    bool cnt_zero = false;      // the counters are zero (k_publish_turn leaves them so)
-    bool nx_clean = masks_zero; // nx is zero over the active rows (no fill before a push)
-    int64_t prev_mf = 0;        // the entries of the frontier one level back
-    int64_t mu = -1;            // after a pull level: list entries of the still-open vertices (< 0: not counted)
-    bool level0_sparse = false, last_sparse = false;
-    unsigned long long se_pub[TGO_MAX_SOURCES] = {};   // the per-source entries the last settle published
-    const volatile unsigned long long* hw = reinterpret_cast<volatile unsigned long long*>(s.hcnt);
-    for (int L = 0; L < depth && qlen > 0; ++L) {
-        const bool stay = pulled && mu >= 0 && stay_gamma > 0.0 &&
-                          static_cast<double>(mu) <= stay_gamma * static_cast<double>(mf);
-        const bool use_pull = stay || static_cast<double>(mf) * ms_alpha > static_cast<double>(total);
-        DevSpan span(st, "msbfs.level", {"level", L}, {"pull", use_pull ? 1 : 0});
-        if ((rc = ms_planes_for(ctx, L + 1))) return rc;
-        const bool queued_before = queued;
-        if (!use_pull && !queued) {     // the frontier's queue, for the push level's scan
-            if (!cnt_zero) HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), st));
-            HIP_TRY(k_ms_queue(push, g.n_active, fr, s.q[cur], s.qdeg, s.cnt, st));
-        }
-        queued = !use_pull;
-        const bool prev_pull = pulled;
-        pulled = use_pull;
-        bool sums = false;          // this push level's settle sums the per-source entries
-        if (!use_pull && !queued_before) cnt_zero = false;      // ms_queue counted into them
-        bool sparse_level = false;  // this push level runs in the sparse form
-        bool count_open = false;    // this pull level counts mu
-        if (use_pull) {
-            if (!cnt_zero) HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), st));
-            cnt_zero = true;
-            // Split the sources: the pull's walk of a vertex stops once every open source is
-            // covered, and one source whose frontier never reaches the vertex (a source far
-            // from it, or one whose sweep is over) makes every walk scan its whole list.  The
-            // sources with the smallest frontiers (exact push entries per source, within a
-            // budget of split_frac of the list entries; every source with an empty frontier)
-            // are pushed into candidate masks instead, and the pull covers only the rest.
-            // (tried at the first pull level of a run of pull levels, where the frontiers
-            // are most unequal; later pull levels found nothing to split on RMAT-24)
-            uint64_t sparse = 0;
-            if (split_frac > 0.0 && !prev_pull) {
-                // every source's exact push entries in one pass, then the smallest within the budget
-                // after a push level its settle summed them already (srcent_ready)
-                // (published with that level's counts: no copy, no stream synchronisation here)
-                static const bool srcent_check = env_double("TGO_MS_SRCENT_CHECK", 0.0) != 0.0;
-                if (srcent_ready && srcent_check) {     // dev check: the settle's sums = a pass of their own
-                    HIP_TRY(k_ms_source_entries(push, fr, g.n_active, full, s.ms_stat, st));
-                    unsigned long long x[TGO_MAX_SOURCES];
-                    HIP_TRY(hipMemcpyAsync(x, s.ms_stat, sizeof(x), hipMemcpyDeviceToHost, st));
-                    HIP_TRY(hipStreamSynchronize(st));
-                    if (std::memcmp(x, se_pub, sizeof(x)) != 0)
-                        return fail(ctx, TGO_E_HIP, "multi-source BFS: settle per-source entries differ from ms_source_entries");
-                    if (trace) std::fprintf(stderr, "[tgo] ms level %d: settle per-source entries checked\n", L);
-                }
-                unsigned long long se[TGO_MAX_SOURCES];
-                if (srcent_ready) {
-                    std::memcpy(se, se_pub, sizeof(se));
-                } else {
-                    s.ms_srcent_zero = false;
-                    HIP_TRY(k_ms_source_entries(push, fr, g.n_active, full, s.ms_srcent, st));
-                    HIP_TRY(hipMemcpyAsync(se, s.ms_srcent, sizeof(se), hipMemcpyDeviceToHost, st));
-                    HIP_TRY(hipStreamSynchronize(st));
-                }
-                int order[TGO_MAX_SOURCES];
-                for (int r = 0; r < nseeds; ++r) order[r] = r;
-                std::sort(order, order + nseeds, [&](int a, int b) { return se[a] < se[b]; });
-                const double budget = split_frac * static_cast<double>(total);
-                double used = 0.0;
-                for (int i = 0; i < nseeds; ++i) {
-                    const int r = order[i];
-                    if (used + static_cast<double>(se[r]) > budget) break;
-                    used += static_cast<double>(se[r]);
-                    sparse |= 1ULL << r;
-                }
-                if (sparse == full) sparse = 0;            // nothing left to pull: plain pull
-                if (sparse) {
-                    bool any = false;
-                    for (int r = 0; r < nseeds; ++r) any |= ((sparse >> r) & 1ULL) && se[r] > 0;
-                    if (!nx_clean) HIP_TRY(hipMemsetAsync(nx, 0, g.n_active * 8, st));
-                    if (any) {                           // push the sparse sources' frontiers
-                        HIP_TRY(k_ms_queue(push, g.n_active, fr, s.q[cur ^ 1], s.qdeg, s.cnt, st, sparse));
-                        const unsigned long long sseq = ++s.pub_seq;         // the counters zero again after it
-                        HIP_TRY(k_publish_turn(s.cnt, s.hcnt_dev, sseq, nullptr, st));
-                        if ((rc = wait_publish(ctx, sseq))) return rc;
-                        const int64_t sq = static_cast<int64_t>(s.hcnt->qlen);
-                        if (sq > 0) {
-                            if ((rc = scan_frontier(ctx, sq))) return rc;
-                            HIP_TRY(k_ms_push(push, s.q[cur ^ 1], s.qpre, sq, fr, s.ms_vis, nx, st, PackTouch{}, sparse));
-                        }
-                    }
-                    if (trace) std::fprintf(stderr, "[tgo] ms level %d split: %d sparse sources, %.0f push entries\n", L,
-                                            __builtin_popcountll(sparse), used);
-                }
-            }
-            if (filter) HIP_TRY(k_ms_fbitmap(fr, n, s.ms_fbm, st));
-            // The first pull level of a run walks long lists to their end (its frontiers are the
-            // most unequal: few walks are covered early).  Opt-in split (TGO_TUNE_MS_COLD /
-            // TGO_MS_COLD=1): the walk covers the hot head only, a blocked pass over the cold
-            // entries in (segment, row) order ORs the open rows' cold masks from L2, ms_finish
-            // settles those rows — same masks, same result.  Measured slower at RMAT-24 (level 2
-            // 2.01 -> 2.69 ms, sweep 4.54 -> 5.22 ms, gpurun_out/r04m): of the level's 227 M
-            // gathers only 44 M are cold (profiles/r04l_ms_diag.log), and the pass streams every
-            // cold entry of every row to reach them.
-            MsColdSplit cs;
-            static const bool cold_env = env_double("TGO_MS_COLD", 0.0) != 0.0;
-            const bool cold_on = ctx->ms_cold < 0 ? cold_env : ctx->ms_cold != 0;
-            if (cold_on && !prev_pull && !filter) {
-                if ((rc = ms_cold_layout(ctx, a->scope, pull, ctx->ms_cold))) return rc;
-                if (g.msc_C > 0) {
-                    cs.hot_lim = g.msc_hot;
-                    cs.acc = s.ms_cacc;
-                    cs.need = s.ms_need;
-                }
-            }
-            // mu for the next level's direction.  The rows a cold split leaves to ms_finish are
-            // not in it: no stay rule after such a level.  Counted once the frontier shrinks (mf
-            // below the level before), since only then can the next level fall under the push
-            // threshold: the count is one more atomic per block, 9 - 25 us at RMAT-24's two
-            // large levels.
-            count_open = stay_gamma > 0.0 && !cs.acc && mf < prev_mf;
-            HIP_TRY(k_ms_pull(pull, push, g.n_active, full, fr, filter ? s.ms_fbm : nullptr, s.ms_vis, nx,
-                              ms_planes(ctx), s.cnt, L + 1, st, filter ? filter_from : 0, full & ~sparse,
-                              sparse ? nx : nullptr, cs, count_open, cs.acc ? 0 : head));   // hot_lim's cut rule as it was
-            if (cs.acc) {
-                HIP_TRY(k_ms_cold(g.msc_adj, g.msc_row, g.msc_C, fr, s.ms_need, s.ms_cacc, st));
-                HIP_TRY(k_ms_finish(push, g.n_active, full, s.ms_vis, nx, sparse ? nx : nullptr, ms_planes(ctx), s.cnt,
-                                    L + 1, s.ms_need, s.ms_cacc, st));
-            }
-        } else {
-            // candidates only land on rows with entries (< n_active); the tail is never read
-            // one kernel zeroes the counters, the candidate masks and the scan's tail entry
-            // (three fills of ~5 us launch each before)
-            // (the counters only when a queue build counted into them, the masks only when nx
-            // is not known to be zero: after a dense push or a pull)
-            HIP_TRY(k_level_prep(cnt_zero ? nullptr : s.cnt, nx, nx_clean ? 0 : g.n_active, s.qdeg + qlen, st));
-            cnt_zero = true;
-            // A small frontier of long lists pushes target-ranged (k_ms_push_ranged: XCD x on
-            // the x-th eighth of the (target range, entry) enumeration, its ranges' masks in
-            // its L2); TGO_MS_PUSH_RANGE = log2 of the range (0 = off).
-            const int64_t rng = static_cast<int64_t>(1) << std::min(40, std::max(0, push_range_log2));
-            const int64_t nr = (g.n_active + rng - 1) / rng;
-            const bool ranged = push_range_log2 > 0 && mf >= push_range_min && nr > 1 &&
-                                (nr + 1) * qlen <= kMsRangePairs && nr * qlen + 1 <= n + 2;
-            // the sparse form: the frontier (queued, as for every push) has little to push (the
-            // ranged push is for large frontiers and does not combine with it)
-            sparse_level = sparse_frac > 0.0 && !ranged &&
-                           (L == 0 || static_cast<double>(mf) <= sparse_frac * static_cast<double>(g.n_active));
-            sums = split_frac > 0.0 && (L == 0 || static_cast<double>(mf) * ms_alpha * 64.0 > static_cast<double>(total));
-            if (ranged) {
-                for (int b = 0; b < 2; ++b)
-                    if (!s.ms_rp[b]) HIP_TRY(dev_alloc(ctx, s.ms_rp[b], kMsRangePairs));
-                const bool light = static_cast<double>(reached) < push_light * static_cast<double>(n);
-                HIP_TRY(k_ms_push_ranged(push, s.q[cur], qlen, g.n_active, rng, s.ms_rp[0], s.ms_rp[1], s.qdeg, s.qpre,
-                                         s.cub_tmp, s.cub_bytes, fr, light ? nullptr : s.ms_vis, nx, st));
-            } else {
-            HIP_TRY(scan_exclusive_i64(s.cub_tmp, s.cub_bytes, s.qdeg, s.qpre, qlen + 1, st));   // tail zeroed above
-            if (sparse_level)
-                HIP_TRY(k_ms_push_sparse(push, s.q[cur], s.qpre, qlen, fr, s.ms_vis, nx, s.q[cur ^ 1], s.cnt, st));
-            else {
-            // While few vertices are reached the push skips the reached-mask read of its
-            // targets (ms_settle drops the reached bits anyway): one random 8-byte read less
-            // per entry at the second level's 12.7 M entries (RMAT-24).  TGO_MS_PUSH_PROBE=0
-            // also drops the read of the candidate mask before the atomic there.
-            const bool light = static_cast<double>(reached) < push_light * static_cast<double>(n);
-            HIP_TRY(k_ms_push(push, s.q[cur], s.qpre, qlen, fr, light ? nullptr : s.ms_vis, nx, st, PackTouch{}, ~0ULL,
-                              light ? push_probe : true));
-            }
-            }
-            // the new frontier's push entries per source, for the next level's split — when that
-            // level may pull (this frontier's entries within 64x of the pull threshold; a
-            // frontier grows at most ~40x a level on RMAT-24), else the split computes them
-            // (level 0: the seeds' entries are not known, so always)
-            if (sums && !s.ms_srcent_zero) HIP_TRY(hipMemsetAsync(s.ms_srcent, 0, 64 * sizeof(unsigned long long), st));
-            if (sums) s.ms_srcent_zero = false;
-            // a frontier within 8x of the pull threshold: the next level will likely pull and
-            // needs no queue — settle and count only (ms_queue builds it if the level pushes)
-            const bool next_pull = static_cast<double>(mf) * ms_alpha * 8.0 > static_cast<double>(total);
-            if (sparse_level) {
-                HIP_TRY(k_ms_settle_sparse(push, s.q[cur ^ 1], s.qdeg, s.ms_vis, nx, ms_planes(ctx), s.cnt, L + 1, st,
-                                           sums ? s.ms_srcent : nullptr, s.q[cur], qlen, fr));
-            } else if (next_pull) {
-                HIP_TRY(k_ms_settle_count(push, g.n_active, s.ms_vis, nx, ms_planes(ctx), s.cnt, L + 1, st,
-                                          sums ? s.ms_srcent : nullptr));
-                queued = false;
-            } else {
-                HIP_TRY(k_ms_settle(push, g.n_active, s.ms_vis, nx, ms_planes(ctx), s.q[cur ^ 1], s.qdeg, s.cnt, L + 1,
-                                    st, sums ? s.ms_srcent : nullptr));
-            }
-        }
-        srcent_ready = !use_pull && sums;
-        {
-            // publish the counts, then queue the next level's direction-independent prefix (its
-            // level planes, zeroed counters) before the host waits: the GPU runs it during the
-            // host's round trip (≈ 10–25 us a level)
-            // (the same launch zeroes the counters, and publishes and zeroes the per-source sums)
-            const unsigned long long seq = ++s.pub_seq;
-            HIP_TRY(k_publish_turn(s.cnt, s.hcnt_dev, seq, sums ? s.ms_srcent : nullptr, st));
-            cnt_zero = true;
-            if (sums) s.ms_srcent_zero = true;
-            if (L + 1 < depth && (rc = ms_planes_for(ctx, L + 2))) return rc;
-            if ((rc = wait_publish(ctx, seq))) return rc;
-        }
-        qlen = static_cast<int64_t>(s.hcnt->qlen);
-        prev_mf = mf;
-        mf = static_cast<int64_t>(s.hcnt->mf);
-        mu = count_open ? static_cast<int64_t>(s.hcnt->open) : -1;
-        if (sums)
-            for (int r = 0; r < TGO_MAX_SOURCES; ++r) se_pub[r] = hw[kPublishExtra + r];
-        reached += qlen;
-        // the consumed frontier's masks were cleared by the sparse settle: zero when they are nx
-        nx_clean = sparse_level;
-        last_sparse = sparse_level;
-        if (L == 0) level0_sparse = sparse_level;
-        if (trace) std::fprintf(stderr, "[tgo] ms level %d %s -> %lld vertices, %lld entries, %llu source-bits%s\n", L,
-                                use_pull ? "pull" : "push", (long long)qlen, (long long)mf, s.hcnt->red[0],
-                                use_pull ? (stay ? " (stayed in pull)" : "") : (sparse_level ? " (sparse)" : ""));
-        if (trace && count_open) std::fprintf(stderr, "[tgo]   %lld list entries of still-open vertices\n", (long long)mu);
-        static const bool diag = env_double("TGO_MS_DIAG", 0.0) != 0.0;
-        if (trace && diag && use_pull) {
-            unsigned long long d[kMsDiagWords] = {};
-            HIP_TRY(k_ms_diag_take(d, st));
-            std::fprintf(stderr, "[tgo]   pull: %llu entries examined, %llu hot / %llu cold mask gathers, %llu open vertices, "
-                         "%llu stopped early; long lists: %llu, %llu entries examined (%llu hot / %llu cold gathers), "
-                         "%llu stopped early\n", d[0], d[1], d[2], d[3], d[4], d[6], d[5], d[8], d[9], d[7]);
-            std::fprintf(stderr, "[tgo]   long lists covered within 4 / 8 / 16 / 32 / 64 entries: %llu / %llu / %llu / %llu / %llu, "
-                         "later %llu, never %llu (head %lld)\n", d[10], d[11], d[12], d[13], d[14], d[15], d[16],
-                         static_cast<long long>(head));
-        }
-        std::swap(fr, nx);
-        cur ^= 1;
-        ++levels;
-    }
-    if (qlen > 0 && a->max_depth > depth)
-        return fail(ctx, TGO_E_UNSUPPORTED, "multi-source BFS stores levels as uint16: depth > 65534");
-    HIP_TRY(hipEventRecord(ctx->ev1, st));
-    HIP_TRY(hipEventSynchronize(ctx->ev1));
-    trace_resolve(st);
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->st.last_kernel_ms = ms;
-    ctx->st.levels = levels;
-    ctx->st.iterations = a->max_depth;
-    // the last level was sparse and found nothing: its frontier's masks are cleared, nothing was
-    // written to the other buffer; ms_fr's entry-less tail (seeds only) was cleared at level 0
-    s.ms_masks_zero = level0_sparse && last_sparse && qlen == 0;
-    if (a->flags & TGO_FLAG_STATS) {
-        HIP_TRY(hipMemsetAsync(s.ms_stat, 0, 2 * TGO_MAX_SOURCES * sizeof(unsigned long long), st));
-        HIP_TRY(k_ms_reach(pull, s.ms_vis, n, nseeds, s.ms_stat, s.ms_stat + TGO_MAX_SOURCES, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    if (dist_out)
-        for (int r = 0; r < nseeds; ++r) {
-            HIP_TRY(k_ms_extract(ms_planes(ctx), s.ms_nplanes, s.ms_vis, g.perm, r, s.msg, n, st));
-            HIP_TRY(hipMemcpyAsync(dist_out + static_cast<int64_t>(r) * n, s.msg, n * sizeof(int64_t),
-                                   hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-    return TGO_OK;
-}
-
-int tgo_copy_multi_distances(tgo_ctx* ctx, int32_t source, int64_t* dist_out) {
-    if (!ctx || !dist_out) return TGO_E_INVALID;
-    Scratch& s = ctx->sc;
-    if (!ctx->loaded || !s.ms_vis) return fail(ctx, TGO_E_STATE, "no multi-source BFS has run");
-    if (source < 0 || source >= s.ms_nsrc) return fail(ctx, TGO_E_INVALID, "source index out of range");
-    (void)hipSetDevice(ctx->opts.device);
-    HIP_TRY(k_ms_extract(ms_planes(ctx), s.ms_nplanes, s.ms_vis, ctx->g.perm, source, s.msg, ctx->g.n, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dist_out, s.msg, ctx->g.n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return TGO_OK;
-}
-
-int tgo_multi_stats(tgo_ctx* ctx, int64_t* reached, int64_t* reached_entries) {
-    if (!ctx) return TGO_E_INVALID;
-    Scratch& s = ctx->sc;
-    if (!ctx->loaded || !s.ms_vis) return fail(ctx, TGO_E_STATE, "no multi-source BFS has run");
-    (void)hipSetDevice(ctx->opts.device);
-    std::vector<unsigned long long> h(2 * TGO_MAX_SOURCES);
-    HIP_TRY(hipMemcpy(h.data(), s.ms_stat, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    for (int r = 0; r < s.ms_nsrc; ++r) {
-        if (reached) reached[r] = static_cast<int64_t>(h[r]);
-        if (reached_entries) reached_entries[r] = static_cast<int64_t>(h[TGO_MAX_SOURCES + r]);
-    }
-    return TGO_OK;
-}
-
-int tgo_copy_distances(tgo_ctx* ctx, int64_t* dist_out) {
-    if (!ctx || !dist_out) return TGO_E_INVALID;
-    if (!ctx->loaded) return fail(ctx, TGO_E_STATE, "no graph loaded");
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(k_unpermute_i64(ctx->sc.dist, ctx->g.perm, ctx->sc.msg, ctx->g.n, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dist_out, ctx->sc.msg, ctx->g.n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return TGO_OK;
 }
 
@@ -2265,8 +1091,8 @@ int tgo_triangles(tgo_ctx* ctx, const tgo_tri_args* a, int64_t* tri_out, tgo_tri
     HIP_TRY(hipMemsetAsync(g.tri_tot + 1, 0, 15 * sizeof(unsigned long long), st));
     {
         DevSpan span(st, "triangles.count", {"forward_entries", g.tri_fnnz}, {"max_forward", g.tri_max_fwd});
-        HIP_TRY(k_tri_count(g.tri_foff, g.tri_fadj, n, ctx->tri_wave_row < 0 ? kTriWaveRow : ctx->tri_wave_row,
-                            ctx->tri_block_row < 0 ? kTriBlockRow : ctx->tri_block_row, g.tri_max_fwd, tri, s.level,
+        HIP_TRY(k_tri_count(g.tri_foff, g.tri_fadj, n, tuned(ctx->tri_wave_row, kTriWaveRow),
+                            tuned(ctx->tri_block_row, kTriBlockRow), g.tri_max_fwd, tri, s.level,
                             s.q[0], &g.tri_tot[5], st));
     }
     {
@@ -2550,57 +1376,18 @@ int tgo_load_partition_layout(tgo_ctx* ctx, int64_t n_global, int64_t lo, int64_
     HostGraph h;
     std::string err;
     // device assembly (assemble.hip) unless TGO_HOST_ASSEMBLY=1
-    const bool on_dev = env_i64("TGO_HOST_ASSEMBLY", 0) == 0;
+    const bool on_dev = !host_assembly();
     int rc = on_dev ? assemble_partition_device(edges, n_global, lo, hi, opts, ctx->opts.hard_query_limit, layout_global,
                                                 h, ctx->stream, err)
                     : assemble_partition(edges, n_global, lo, hi, opts, ctx->opts.hard_query_limit, layout_global, h,
                                          threads_of(ctx), err);
-    if (rc == TGO_OK && env_i64("TGO_TRACE", 0))
+    if (rc == TGO_OK && trace_on())
         std::fprintf(stderr, "[tgo] load_partition assembly (%s) %8.1f ms\n", on_dev ? "device" : "host",
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     if (rc) return fail(ctx, rc, err);
     rc = tgo::part_upload(ctx, h, n_global, lo);
     ctx->st.load_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return rc;
-}
-
-static int part_check(tgo_ctx* ctx);
-
-
-static int part_check(tgo_ctx* ctx) {
-    if (!ctx) return TGO_E_INVALID;
-    if (!ctx->loaded || !ctx->g.partitioned) return fail(ctx, TGO_E_STATE, "no partitioned graph loaded");
-    (void)hipSetDevice(ctx->opts.device);
-    return TGO_OK;
-}
-
-// Entry points that leave work queued: on a ctx-owned stream the caller cannot order its
-// collectives after that work, so finish it before returning; on the caller's stream the
-// work stays stream-ordered (the caller's collectives follow it on the same stream).
-static int part_done(tgo_ctx* ctx) {
-    if (ctx->own_stream) HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return TGO_OK;
-}
-
-// Level counters {next queue length, its push entries}.  Host mode: read (one stream sync)
-// into counts.  Device mode (tgo_part_device_counts): published to the caller's device
-// buffer without a sync — the caller all-reduces it and reads the global counts once; the
-// local queue length is fetched lazily by the next call that needs it (part_qlen_now).
-static int part_counts(tgo_ctx* ctx, int64_t* counts, bool device_ok = true) {
-    if (ctx->part_dcounts && device_ok) {
-        HIP_TRY(k_publish_counts(ctx->sc.cnt, ctx->part_dcounts, ctx->part_qlen_dev, ctx->stream));
-        ctx->part_qlen_stale = true;
-        return part_done(ctx);
-    }
-    int rc = read_counters(ctx);
-    if (rc) return rc;
-    ctx->part_qlen = static_cast<int64_t>(ctx->sc.hcnt->qlen);
-    ctx->part_qlen_stale = false;
-    if (counts) {
-        counts[0] = ctx->part_qlen;
-        counts[1] = static_cast<int64_t>(ctx->sc.hcnt->mf);
-    }
-    return TGO_OK;
 }
 
 static int part_qlen_now(tgo_ctx* ctx, int64_t& q) {
@@ -3275,7 +2062,7 @@ int tgo_part_pr_blocked(tgo_ctx* ctx, int32_t world, int64_t active_span, int64_
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (hbad) return fail(ctx, TGO_E_INVALID, "tgo_part_pr_blocked: a source row lies beyond active_span");
     // the mapping is not monotone in the global id: re-sort each row so the device build applies
-    if (env_i64("TGO_HOST_ASSEMBLY", 0) == 0) {
+    if (!host_assembly()) {
         std::string err;
         if (int r = sort_rows_device(g.in.off, nl, gidx, nnz, ctx->stream, err)) return fail(ctx, r, err);
     }
@@ -3881,7 +2668,6 @@ int tgo_sync(tgo_ctx* ctx) {
 
 // accessors for the C++ partitioned driver (part_driver.cpp)
 namespace tgo {
-hipStream_t part_stream(tgo_ctx* ctx) { return ctx->stream; }
 // A partition's host graph onto the device (tgo_load_partition_layout, tgo_load_partition_rows).
 int part_upload(tgo_ctx* ctx, HostGraph& h, int64_t n_global, int64_t lo) {
     free_graph(ctx);
@@ -3927,10 +2713,6 @@ int part_rows_take(tgo_ctx* ctx, RowStaging& st, std::string& err) {
     return TGO_OK;
 }
 void part_drop_staging(tgo_ctx* ctx) { ctx->staging = RowStaging(); ctx->dec.release(); }
-int part_threads(const tgo_ctx* ctx) { return threads_of(ctx); }
-void part_set_live(tgo_ctx* ctx, int64_t live) { ctx->st.num_vertices = live; }
-int part_fail(tgo_ctx* ctx, int code, const std::string& msg) { return fail(ctx, code, msg); }
-int64_t* part_dcounts_of(tgo_ctx* ctx) { return ctx->part_dcounts; }
 // tgo_part_sssp_relax with the exchange header (sizes, 2 * nranks words) written on the device
 int part_sssp_relax_dev(tgo_ctx* ctx, int64_t thr, int32_t nranks, int64_t* send, int64_t* sizes) {
     if (!sizes) return fail(ctx, TGO_E_INVALID, "null sizes");
@@ -4011,7 +2793,6 @@ int part_sssp_split(tgo_ctx* ctx, int64_t delta, bool* on) {
     }
     return part_done(ctx);
 }
-bool part_sssp_devloop(const tgo_ctx* ctx) { return ctx->part_devloop; }
 // One phase of the device-sized loop, relax half: commit + relax of the current queue (remote
 // targets marked), then the exchange header (sizes, 4 words per rank) and the pack.
 // fold (one rank only, may be null): the header's fold (part_sssp_header_read's 5 words) read
@@ -4094,7 +2875,6 @@ void part_ms_bypass(tgo_ctx* ctx, uint64_t* cand_global, int self) {
     ctx->part_ms_cand = cand_global;
     ctx->part_ms_self = cand_global ? self : -1;
 }
-std::shared_ptr<void>& part_state_of(tgo_ctx* ctx) { return ctx->part_state; }
 int part_in_list(tgo_ctx* ctx, const int32_t** adj, int64_t* nnz) {
     if (int rc = part_check(ctx)) return rc;
     *adj = ctx->g.in.adj;
@@ -4107,8 +2887,6 @@ int part_out_list(tgo_ctx* ctx, const int32_t** adj, int64_t* nnz) {
     *nnz = ctx->g.out.nnz;
     return TGO_OK;
 }
-// ghost exchange of the dense multi-source levels (tgo_set_tuning TGO_TUNE_MS_GHOST; default on)
-bool ms_ghost_of(const tgo_ctx* ctx) { return ctx->ms_ghost != 0; }
 // the blocked gathered layout of the last tgo_part_pr_blocked (world 0: plain layout)
 int part_pr_layout_of(tgo_ctx* ctx, int32_t* world, int64_t* hot, int64_t* span) {
     if (int rc = part_check(ctx)) return rc;
@@ -4138,32 +2916,6 @@ int part_scratch(tgo_ctx* ctx, void** p, int64_t bytes, int slot) {
     }
     *p = s.drv[slot];
     return TGO_OK;
-}
-// Push budget of the multi-source pull levels' sparse sources (the source split), as a
-// fraction of the list entries: the ctx's tgo_set_tuning value, else TGO_MS_SPLIT, else 0.5 %.
-double ms_split_of(const tgo_ctx* ctx) {
-    static const double env = env_double("TGO_MS_SPLIT", 0.005);
-    return ctx->ms_split >= 0.0 ? ctx->ms_split : env;
-}
-// gamma of the stay-in-pull rule and the sparse push levels' fraction of n_active (tgo_bfs_multi):
-// the ctx's tgo_set_tuning value, else TGO_MS_STAY / TGO_MS_SPARSE, else the defaults.
-double ms_stay_of(const tgo_ctx* ctx) {
-    static const double env = std::max(0.0, env_double("TGO_MS_STAY", kMsStayDefault));
-    return ctx->ms_stay >= 0.0 ? ctx->ms_stay : env;
-}
-double ms_sparse_of(const tgo_ctx* ctx) {
-    static const double env = std::max(0.0, env_double("TGO_MS_SPARSE", kMsSparseDefault));
-    return ctx->ms_sparse >= 0.0 ? ctx->ms_sparse : env;
-}
-// Head probe of ms_pull's long lists, in entries: the ctx's tgo_set_tuning value, else TGO_MS_HEAD,
-// else the default.
-int64_t ms_head_of(const tgo_ctx* ctx) {
-    static const int64_t env = [] {
-        const double v = env_double("TGO_MS_HEAD", static_cast<double>(kMsHeadDefault));
-        if (!(v >= 0.0)) return int64_t(0);                                  // negative or not a number
-        return static_cast<int64_t>(std::min(v, static_cast<double>(kMsHeadMax)));   // clamped before the cast
-    }();
-    return ctx->ms_head >= 0 ? ctx->ms_head : env;
 }
 
 }  // namespace tgo

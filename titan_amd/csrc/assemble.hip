@@ -479,7 +479,7 @@ int assemble_edges_device(const tgo_edges* e, const tgo_load_opts* opts, int64_t
     const int bits = 2 * b;
 
     // TGO_TRACE=1: per-phase times on stderr (synchronising the stream at each phase end)
-    static const bool trace = std::getenv("TGO_TRACE") && std::atoi(std::getenv("TGO_TRACE")) != 0;
+    static const bool trace = trace_on();
     auto t_last = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
         if (!trace && !tracing()) return;
@@ -745,7 +745,7 @@ int assemble_partition_device(const tgo_edges* e, int64_t n_global, int64_t lo, 
     int br = 1;                   // row bits (local ids)
     while ((int64_t(1) << br) < n) ++br;
     const int bits = b + br;
-    static const bool trace = std::getenv("TGO_TRACE") && std::atoi(std::getenv("TGO_TRACE")) != 0;
+    static const bool trace = trace_on();
     auto t_last = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
         if (!trace && !tracing()) return;

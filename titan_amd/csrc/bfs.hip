@@ -390,12 +390,12 @@ hipError_t k_bu_step(const View& pull, const View& push, int64_t n, const uint64
     // with thousands of others.
     const int64_t words = (n + 63) / 64;
     // TGO_BFS_SERIAL: lists up to this many entries are scanned by their own lane (kSerialScan default)
-    static const int64_t serial = [] { const char* e = std::getenv("TGO_BFS_SERIAL"); return e ? std::atoll(e) : kSerialScan; }();
+    static const int64_t serial = env_i64("TGO_BFS_SERIAL", kSerialScan);
     // TGO_BFS_BU_STEP (A/B): entries per dependent round trip of a lane's own list — 2 since the
     // trips are branch-free (round 6, RMAT-24 16 roots, one box: 4 -> 2 hmean 360 -> 374 GTEPS,
     // 8: 313; a second box: 2 371, 4 374, 1 363 — 2 and 4 within noise there;
     // profiles/r06bu_bfs_bu_step_ab.log)
-    static const int bs = [] { const char* e = std::getenv("TGO_BFS_BU_STEP"); return e ? std::atoi(e) : 2; }();
+    static const int bs = static_cast<int>(env_i64("TGO_BFS_BU_STEP", 2));
     // 2048 blocks (8192 waves: one resident round at 8 waves per SIMD), each wave walking 32
     // words at RMAT-24: hmean 326-331 -> 368-371 GTEPS over the 64 bench roots against 8192
     // blocks (4096: 346-360, 1024: 327, 16384: 276-279; profiles/r05bg_bfs_bu_grid_ab.log).

@@ -1,0 +1,291 @@
+// ctx.hpp — the context behind the C-ABI's opaque tgo_ctx, and the helpers that the driver
+// files (api.cpp, api_traverse.cpp, api_msbfs.cpp, part_driver.cpp) share.  A function used by
+// more than one of them is declared here, once.  Private to titan_amd/csrc: never installed.
+#pragma once
+#include <algorithm>
+#include <atomic>
+#include <memory>
+#include <string>
+#include <utility>
+#include <vector>
+#include <hip/hip_runtime_api.h>
+#include "engine.hpp"
+#include "trace.hpp"
+#include "../../include/titan_gpu_olap_part.h"
+
+struct tgo_ctx {
+    tgo_options opts{};
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    std::string err;
+    tgo::RowStaging staging;
+    tgo::DevGraph g;
+    bool loaded = false;
+    std::vector<int64_t> titan_id;
+    std::vector<int32_t> perm;                       // row-order dense -> internal
+    // Titan id -> dense (seed lookups, tgo_dense_ids): binary search over titan_id when it is
+    // strictly increasing (edge loads; row loads of an ordered scan usually), else over a
+    // sorted copy built on the first lookup — no per-load hash map (16.8 M inserts at RMAT-24)
+    bool id_sorted = false;
+    std::vector<std::pair<int64_t, int32_t>> id_index;
+    tgo::Scratch sc;
+    tgo_stats st{};
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    int64_t dev_bytes = 0;
+    std::vector<void*> allocs;
+    int part_cur = 0;           // partitioned BFS: queue buffer holding the frontier
+    int64_t part_qlen = 0;      // its length
+    bool part_queued = true;    // q[part_cur] holds the frontier (pull / bottom-up levels only count it)
+    // native multi-source sweep (part_driver.cpp): this rank's slice of the candidate words is
+    // not packed but ORed in directly (tgo::part_ms_bypass); -1 = every slice packed
+    int part_ms_self = -1;
+    uint64_t* part_ms_cand = nullptr;
+    const uint64_t* part_frontier = nullptr;   // after bottom-up: the caller's nb_local (queued lazily)
+    int64_t* part_dcounts = nullptr;    // caller's device counts (tgo_part_device_counts)
+    int64_t* part_qlen_dev = nullptr;   // device copy of the queue length (lazy host read)
+    bool part_qlen_stale = false;       // part_qlen must be read from part_qlen_dev
+    double part_alpha = 0.85, part_base = 0.0;
+    int32_t part_pr_iter = 0;   // partitioned PageRank: iteration reached / program length
+    int32_t part_pr_iters = 0;
+    int32_t part_pr_world = 0;  // blocked gathered layout (tgo_part_pr_blocked): world, H, A
+    bool part_pr_plain = false; // tgo_part_pr_plain: the plain layout although the blocked one is built
+    int64_t part_pr_hot = 0, part_pr_span = 0;
+    int64_t part_relaxed = 0;   // partitioned SSSP: entries relaxed, phases
+    int32_t part_phases = 0;
+    int64_t part_seed = -1;     // partitioned SSSP: the seed's internal id when owned here
+    bool part_split = false;    // partitioned SSSP run on the light/heavy split (part_sssp_split)
+    bool part_devloop = false;  // ... and on the device-sized loop (delta_loop.hip, part_sssp_dev_*)
+    tgo::EdgeProg edge_prog;        // tgo_set_edge_program (TGO_EDGE_PROGRAM gathers)
+    int64_t pv_max_out = 0, pv_max_in = 0;   // largest OUT / IN list of a vertex cut
+    std::vector<int64_t> pv_rows;            // row ids of the vertex cuts
+    // last finished program whose compute keys tgo_result_rows can encode (-1 = none)
+    int res_kind = -1;
+    bool host_decode = false;                // TGO_HOST_DECODE latched for the load in progress
+    tgo::DecodeScratch dec;                  // device row decoder buffers (decode.hip)
+    bool res_empty = false;                  // it set no property (PageRank iterations(0))
+    tgo::ResultSource res_src;
+    int num_cus = 256;          // compute units of the device (persistent launches)
+    double ms_split = -1.0;     // tgo_set_tuning(TGO_TUNE_MS_SPLIT); < 0: TGO_MS_SPLIT / the default
+    int ms_ghost = 1;           // tgo_set_tuning(TGO_TUNE_MS_GHOST): dense partitioned levels exchange ghosts
+    int ds_bins = -1;           // tgo_set_tuning(TGO_TUNE_DS_BINS): 1 / 0; < 0: TGO_DS_BINS / on
+    int64_t ds_pile_cap = 0;    // tgo_set_tuning(TGO_TUNE_DS_PILE_CAP): entries per pile; 0 = n
+    int ds_done = -1;           // tgo_set_tuning(TGO_TUNE_DS_DONE): 1 / 0; < 0: TGO_DS_DONE / off
+    double ds_pull = -1;        // tgo_set_tuning(TGO_TUNE_DS_PULL): member fraction; < 0: TGO_DS_PULL / off
+    int ds_small = -1;          // tgo_set_tuning(TGO_TUNE_DS_SMALL): 1 / 0; < 0: TGO_DS_SMALL / off
+    unsigned long long* part_srcent = nullptr;   // next settle's per-source sums (part_ms_settle_sums)
+    bool part_count_only = false;               // next settle: no queue (part_ms_settle_sums)
+    uint64_t* part_own_next = nullptr;          // next push: owned targets straight into these masks
+    uint64_t* part_own_direct = nullptr;        // the last push did so (its settle skips the own OR)
+    int64_t ms_cold = -1;       // tgo_set_tuning(TGO_TUNE_MS_COLD): 0 off, 1 on, > 1 on with that
+                                // hot head (and segment); < 0: TGO_MS_COLD / on
+    double ms_stay = -1.0;      // tgo_set_tuning(TGO_TUNE_MS_STAY): gamma; < 0: TGO_MS_STAY / the default
+    double ms_sparse = -1.0;    // tgo_set_tuning(TGO_TUNE_MS_SPARSE): fraction of n_active; < 0: TGO_MS_SPARSE / the default
+    int64_t ms_head = -1;       // tgo_set_tuning(TGO_TUNE_MS_HEAD): entries, 0 = off; < 0: TGO_MS_HEAD / the default
+    int64_t tri_wave_row = -1;  // tgo_set_tuning(TGO_TUNE_TRI_WAVE_ROW / _BLOCK_ROW): forward-row lengths from
+    int64_t tri_block_row = -1; // which a wave / a workgroup takes the row; < 0: the defaults (kTriWaveRow / kTriBlockRow)
+    int64_t tri_max = 0;        // largest count of the last tgo_triangles (an Integer key's range check)
+    // state a native partitioned driver keeps between runs on this graph (part_driver.cpp:
+    // the PageRank ghost lists); dropped with the graph
+    std::shared_ptr<void> part_state;
+};
+
+namespace tgo {
+
+inline int fail(tgo_ctx* c, int code, const std::string& msg) {
+    if (c) c->err = msg;
+    return code;
+}
+
+#define HIP_TRY(call)                                                              \
+    do {                                                                           \
+        hipError_t e__ = (call);                                                   \
+        if (e__ != hipSuccess)                                                     \
+            return fail(ctx, e__ == hipErrorOutOfMemory ? TGO_E_OOM : TGO_E_HIP,   \
+                        std::string(#call) + ": " + hipGetErrorString(e__));       \
+    } while (0)
+
+template <class T>
+hipError_t dev_alloc(tgo_ctx* ctx, T*& p, int64_t count) {
+    void* q = nullptr;
+    const size_t bytes = static_cast<size_t>(std::max<int64_t>(count, 1)) * sizeof(T);
+    hipError_t e = hipMalloc(&q, bytes);
+    if (e != hipSuccess) return e;
+    ctx->allocs.push_back(q);
+    ctx->dev_bytes += static_cast<int64_t>(bytes);
+    p = static_cast<T*>(q);
+    return hipSuccess;
+}
+
+// Release one dev_alloc array of `count` elements before the graph goes (the stream is
+// synchronised first: queued kernels may still use it).
+template <class T>
+void dev_free(tgo_ctx* ctx, T*& p, int64_t count) {
+    if (!p) return;
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    auto it = std::find(ctx->allocs.begin(), ctx->allocs.end(), static_cast<void*>(p));
+    if (it != ctx->allocs.end()) {
+        ctx->allocs.erase(it);
+        ctx->dev_bytes -= static_cast<int64_t>(std::max<int64_t>(count, 1) * sizeof(T));
+        (void)hipFree(p);
+    }
+    p = nullptr;
+}
+
+// Adopt a device array built on the device (DevArray): no copy, freed with the graph.
+template <class T>
+void adopt(tgo_ctx* ctx, T*& p, DevArray<T>& a) {
+    p = a.p;
+    if (a.p) {
+        ctx->allocs.push_back(a.p);
+        ctx->dev_bytes += static_cast<int64_t>(std::max<int64_t>(a.n, 1) * sizeof(T));
+    }
+    a.p = nullptr;
+    a.n = -1;
+}
+
+template <class T>
+hipError_t upload(tgo_ctx* ctx, T*& p, const std::vector<T>& h) {
+    hipError_t e = dev_alloc(ctx, p, static_cast<int64_t>(h.size()));
+    if (e != hipSuccess || h.empty()) return e;
+    return copy_chunked(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+// ------------------------------------------------------------------ api.cpp
+void free_graph(tgo_ctx* ctx);
+int threads_of(const tgo_ctx* ctx);
+int resolve_seed(tgo_ctx* ctx, int64_t seed, int is_dense, int64_t& out);
+int check_program(tgo_ctx* ctx, int scope);
+// wait_publish for a publish that later ones may have overwritten
+int wait_publish_at_least(tgo_ctx* ctx, unsigned long long seq);
+
+// The helpers of the sweeps' per-level path (wait_publish, read_counters, scan_frontier) are
+// inline: a level loop calls nothing across files for them.
+
+// Counters of the work queued so far, without a copy + stream synchronisation: the publish
+// kernel stores them and then a sequence number into host-mapped memory; the host spins on
+// the sequence number (the level loops read a few words per level, so the wake-up latency of
+// a blocking synchronisation dominated short levels).  A stream error ends the spin.
+//
+// Spin on the publish sequence number (a periodic stream query ends the spin on a failure).
+inline int wait_publish(tgo_ctx* ctx, unsigned long long seq) {
+    Scratch& s = ctx->sc;
+    const volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(s.hcnt) + kCounterWords;
+    for (uint64_t it = 1;; ++it) {
+        if (*flag == seq) break;
+        if ((it & 0x3FFF) == 0) {
+            const hipError_t q = hipStreamQuery(ctx->stream);
+            if (q != hipSuccess && q != hipErrorNotReady) return fail(ctx, TGO_E_HIP, hipGetErrorString(q));
+            if (q == hipSuccess && *flag != seq) return fail(ctx, TGO_E_HIP, "counter publish not visible after the stream drained");
+        }
+        __builtin_ia32_pause();
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return TGO_OK;
+}
+
+inline int read_counters(tgo_ctx* ctx) {
+    Scratch& s = ctx->sc;
+    const unsigned long long seq = ++s.pub_seq;
+    HIP_TRY(k_publish_counters(s.cnt, s.hcnt_dev, seq, ctx->stream));
+    return wait_publish(ctx, seq);
+}
+
+// Exclusive scan of qdeg[0..qlen) into qpre[0..qlen] (qpre[qlen] = total).
+inline int scan_frontier(tgo_ctx* ctx, int64_t qlen) {
+    Scratch& s = ctx->sc;
+    HIP_TRY(hipMemsetAsync(s.qdeg + qlen, 0, sizeof(int64_t), ctx->stream));
+    HIP_TRY(scan_exclusive_i64(s.cub_tmp, s.cub_bytes, s.qdeg, s.qpre, qlen + 1, ctx->stream));
+    return TGO_OK;
+}
+
+// The partitioned primitives (api.cpp) open and close with these three.
+inline int part_check(tgo_ctx* ctx) {
+    if (!ctx) return TGO_E_INVALID;
+    if (!ctx->loaded || !ctx->g.partitioned) return fail(ctx, TGO_E_STATE, "no partitioned graph loaded");
+    (void)hipSetDevice(ctx->opts.device);
+    return TGO_OK;
+}
+
+// Entry points that leave work queued: on a ctx-owned stream the caller cannot order its
+// collectives after that work, so finish it before returning; on the caller's stream the
+// work stays stream-ordered (the caller's collectives follow it on the same stream).
+inline int part_done(tgo_ctx* ctx) {
+    if (ctx->own_stream) HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return TGO_OK;
+}
+
+// Level counters {next queue length, its push entries}.  Host mode: read (one stream sync)
+// into counts.  Device mode (tgo_part_device_counts): published to the caller's device
+// buffer without a sync — the caller all-reduces it and reads the global counts once; the
+// local queue length is fetched lazily by the next call that needs it (part_qlen_now).
+inline int part_counts(tgo_ctx* ctx, int64_t* counts, bool device_ok = true) {
+    if (ctx->part_dcounts && device_ok) {
+        HIP_TRY(k_publish_counts(ctx->sc.cnt, ctx->part_dcounts, ctx->part_qlen_dev, ctx->stream));
+        ctx->part_qlen_stale = true;
+        return part_done(ctx);
+    }
+    int rc = read_counters(ctx);
+    if (rc) return rc;
+    ctx->part_qlen = static_cast<int64_t>(ctx->sc.hcnt->qlen);
+    ctx->part_qlen_stale = false;
+    if (counts) {
+        counts[0] = ctx->part_qlen;
+        counts[1] = static_cast<int64_t>(ctx->sc.hcnt->mf);
+    }
+    return TGO_OK;
+}
+
+// ... and what part_driver.cpp's loops call between them
+int part_upload(tgo_ctx* ctx, HostGraph& h, int64_t n_global, int64_t lo);
+int part_rows_take(tgo_ctx* ctx, RowStaging& st, std::string& err);
+// a failed row load: the staged rows and the decoder's buffers go together
+void part_drop_staging(tgo_ctx* ctx);
+int part_dims(tgo_ctx* ctx, int64_t* n_local, int64_t* lo, int64_t* n_global, int64_t* entries);
+int part_scratch(tgo_ctx* ctx, void** p, int64_t bytes, int slot);
+// this rank's slice of the candidate words bypasses the pack / exchange (ORed in directly by the
+// settle); (nullptr, -1) turns it off
+void part_ms_bypass(tgo_ctx* ctx, uint64_t* cand_global, int self);
+// the next settle sums its new frontier's push entries per source into out (one-shot)
+int part_ms_settle_sums(tgo_ctx* ctx, int64_t* out, bool count_only = false);
+// the next push writes its owned targets straight into next (bypass on); nullptr cancels
+void part_ms_own_next(tgo_ctx* ctx, uint64_t* next);
+// device words to the host through the mapped counter page (no stream synchronisation)
+int part_read_words(tgo_ctx* ctx, const int64_t* dev, int count, int64_t* out);
+int part_in_list(tgo_ctx* ctx, const int32_t** adj, int64_t* nnz);
+int part_out_list(tgo_ctx* ctx, const int32_t** adj, int64_t* nnz);
+int part_pr_layout_of(tgo_ctx* ctx, int32_t* world, int64_t* hot, int64_t* span);
+int part_sssp_relax_dev(tgo_ctx* ctx, int64_t thr, int32_t nranks, int64_t* send, int64_t* sizes);
+int part_sssp_header_fold(tgo_ctx* ctx, const int64_t* own, const int64_t* recv, int nranks, int64_t* out);
+int part_sssp_header_read(tgo_ctx* ctx, const int64_t* own, const int64_t* recv, int nranks, int64_t* out,
+                          int64_t* words);
+int part_sssp_split(tgo_ctx* ctx, int64_t delta, bool* on);
+int part_sssp_dev_relax(tgo_ctx* ctx, int32_t nranks, int64_t* send, int64_t* sizes, int64_t* fold);
+int part_sssp_dev_apply(tgo_ctx* ctx, const int64_t* recv, int64_t npairs);
+int part_sssp_dev_extract(tgo_ctx* ctx, int64_t thr);
+
+// ------------------------------------------------------------------ api_traverse.cpp
+int64_t default_delta(const DevGraph& g, bool weighted);
+
+// ------------------------------------------------------------------ api_msbfs.cpp
+int ms_alloc(tgo_ctx* ctx);
+double ms_split_of(const tgo_ctx* ctx);
+double ms_stay_of(const tgo_ctx* ctx);
+double ms_sparse_of(const tgo_ctx* ctx);
+int64_t ms_head_of(const tgo_ctx* ctx);
+
+inline LevelPlanes ms_planes(tgo_ctx* ctx) { return LevelPlanes{ctx->sc.ms_lvl, ctx->g.n}; }
+
+// Zero the level planes a discovery at `level` writes (planes 0..floor(log2(level))) that
+// this sweep has not zeroed yet: vertices reached earlier have levels < 2^k, whose bit k
+// is 0, so a plane is valid from the moment it is zeroed.
+inline int ms_planes_for(tgo_ctx* ctx, int32_t level) {
+    Scratch& s = ctx->sc;
+    while (s.ms_nplanes < kLevelPlanes && (level >> s.ms_nplanes) != 0) {
+        HIP_TRY(hipMemsetAsync(s.ms_lvl + static_cast<int64_t>(s.ms_nplanes) * ctx->g.n, 0,
+                               ctx->g.n * sizeof(uint64_t), ctx->stream));
+        ++s.ms_nplanes;
+    }
+    return TGO_OK;
+}
+
+}  // namespace tgo

@@ -731,11 +731,6 @@ inline int grid_for(int64_t work, int cap) {
 
 }  // namespace
 
-static long long env_i64_d(const char* name, long long dflt) {
-    const char* e = std::getenv(name);
-    return e ? std::atoll(e) : dflt;
-}
-
 hipError_t k_ds_seed(const View& push, int64_t* dist, int32_t* q, int64_t* qdeg, int64_t seed, hipStream_t s) {
     ds_seed<<<1, 64, 0, s>>>(push, dist, q, qdeg, seed);
     return hipGetLastError();
@@ -784,7 +779,7 @@ hipError_t k_ds_relax_ws_part(const DevCsr& ws, const int64_t* light, const int3
                               const int64_t* msg, int64_t* dist, uint64_t* pend, int32_t* qn, int64_t* qdeg_n,
                               Counters* cnt, int64_t thr, int64_t lo, int64_t n_local, int64_t* rbest, uint64_t* rmark,
                               long long* track, hipStream_t s) {
-    static const bool staged = env_i64_d("TGO_DS_PART_STAGED", 1) != 0;     // A/B: 0 = one entry at a time
+    static const bool staged = env_i64("TGO_DS_PART_STAGED", 1) != 0;     // A/B: 0 = one entry at a time
     if (staged)
         ds_relax_ws_staged<<<256 * 8, kBlock, 0, s>>>(ws.off, ws.adj, ws.w, light, q, qpre, qlen, msg, dist, pend, qn,
                                                       qdeg_n, cnt, thr, lo, n_local, rbest, rmark, track);

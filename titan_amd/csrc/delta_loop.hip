@@ -1132,11 +1132,6 @@ __global__ void __launch_bounds__(kBlock) ds_relax_dc(const int64_t* __restrict_
 
 }  // namespace
 
-static long long env_i64_dl(const char* name, long long dflt) {
-    const char* e = std::getenv(name);
-    return e ? std::atoll(e) : dflt;
-}
-
 hipError_t k_ds_loop_seed(const DevCsr& ws, const int64_t* light, int64_t* dist, int32_t* q, int64_t* qpre, DsLoop* L,
                           int64_t seed, int64_t delta, hipStream_t s) {
     ds_loop_seed<<<1, 64, 0, s>>>(ws.off, light, dist, q, qpre, L, seed, delta);
@@ -1160,7 +1155,7 @@ hipError_t k_ds_loop_step(const DevCsr& ws, const int64_t* light, uint64_t* pend
 hipError_t k_ds_part_relax(const DevCsr& ws, const int64_t* light, uint64_t* pend, uint64_t* member, int64_t* dist,
                            int64_t* msg, int32_t* const q[2], int64_t* const qpre[2], DsLoop* L, int cur, int64_t delta,
                            int64_t lo, int64_t n_local, int64_t* rbest, uint64_t* rmark, hipStream_t s) {
-    static const int cg = static_cast<int>(env_i64_dl("TGO_DS_CGRID", 1024));
+    static const int cg = static_cast<int>(env_i64("TGO_DS_CGRID", 1024));
     ds_commit_dev<false><<<cg, kBlock, 0, s>>>(q[cur], dist, msg, pend, member, L, cur, nullptr);
     ds_relax_dev<false, true><<<256 * 8, kBlock, 0, s>>>(ws.off, ws.adj, ws.w, light, q[cur], qpre[cur], msg, dist, pend,
                                                          q[cur ^ 1], qpre[cur ^ 1], L, cur, delta, 0, nullptr, 0,
@@ -1207,11 +1202,11 @@ hipError_t k_ds_loop_step_small(const DevCsr& ws, const int64_t* light, uint64_t
                                 int64_t delta, int nbins, int32_t* pile, int64_t cap, int32_t* mlist, uint64_t* done,
                                 int64_t scan_above, hipStream_t s) {
     if (nbins < 2 || nbins > kDsMaxBins || nbins > kBlock || cap < 1) return hipErrorInvalidValue;
-    static const int64_t sq = env_i64_dl("TGO_DS_SMALL_Q", 1024);
-    static const int64_t se = env_i64_dl("TGO_DS_SMALL_E", 4096);
-    static const int ss = static_cast<int>(env_i64_dl("TGO_DS_SMALL_STEPS", 64));
-    static const int cg = static_cast<int>(env_i64_dl("TGO_DS_CGRID", 1024));
-    static const int rg = static_cast<int>(env_i64_dl("TGO_DS_RGRID", 256 * 8));
+    static const int64_t sq = env_i64("TGO_DS_SMALL_Q", 1024);
+    static const int64_t se = env_i64("TGO_DS_SMALL_E", 4096);
+    static const int ss = static_cast<int>(env_i64("TGO_DS_SMALL_STEPS", 64));
+    static const int cg = static_cast<int>(env_i64("TGO_DS_CGRID", 1024));
+    static const int rg = static_cast<int>(env_i64("TGO_DS_RGRID", 256 * 8));
     const DsQ qs{q[0], q[1], qpre[0], qpre[1]};
     ds_small_steps<kDsRelaxE><<<1, kBlock, 0, s>>>(ws.off, ws.adj, ws.w, light, pend, member, dist, msg, qs, L, delta,
                                                    nbins, pile, cap, mlist, done, scan_above, ss, sq, se, DsPull{});
@@ -1237,9 +1232,9 @@ hipError_t k_ds_loop_step_bins(const DevCsr& ws, const int64_t* light, uint64_t*
     // grids (TGO_DS_XGRID / _CGRID / _RGRID, A/B): most of a run's ~100 steps have tiny queues
     // and no extraction, and a launch of thousands of blocks that exit at once still costs
     // ~10-15 us; the grid-stride loops take any grid
-    static const int xg = static_cast<int>(env_i64_dl("TGO_DS_XGRID", 0));
-    static const int cg = static_cast<int>(env_i64_dl("TGO_DS_CGRID", 1024));
-    static const int rg = static_cast<int>(env_i64_dl("TGO_DS_RGRID", 256 * 8));
+    static const int xg = static_cast<int>(env_i64("TGO_DS_XGRID", 0));
+    static const int cg = static_cast<int>(env_i64("TGO_DS_CGRID", 1024));
+    static const int rg = static_cast<int>(env_i64("TGO_DS_RGRID", 256 * 8));
     ds_extract_bins<<<xg > 0 ? std::min(xg, extract_grid(words)) : extract_grid(words), kBlock, 0, s>>>(ws.off, light, pend, member, dist, L, cur, pile, cap, mlist,
                                                            done, q[cur], qpre[cur], n, pull);
     ds_commit_dev<true><<<cg, kBlock, 0, s>>>(q[cur], dist, msg, pend, member, L, cur, mlist);
@@ -1249,7 +1244,7 @@ hipError_t k_ds_loop_step_bins(const DevCsr& ws, const int64_t* light, uint64_t*
         ds_pull_flip<<<1, 64, 0, s>>>(L);
     }
     // TGO_DS_RELAX_E=5 (A/B): the round-5 entries per thread of the binned relax (default kDsRelaxE)
-    static const int re = static_cast<int>(env_i64_dl("TGO_DS_RELAX_E", kDsRelaxE));
+    static const int re = static_cast<int>(env_i64("TGO_DS_RELAX_E", kDsRelaxE));
     if (!done_filter && re == 5) {
         ds_relax_dev<true, false, false, 5><<<rg, kBlock, 0, s>>>(ws.off, ws.adj, ws.w, light, q[cur], qpre[cur], msg,
                                                                   dist, pend, q[cur ^ 1], qpre[cur ^ 1], L, cur, delta,

@@ -18,6 +18,7 @@
 #include <vector>
 #include <hip/hip_runtime_api.h>
 #include "../../include/titan_gpu_olap.h"
+#include "env.hpp"
 
 namespace tgo {
 
@@ -477,6 +478,26 @@ struct DevGraph {
     int64_t tri_fnnz = 0, tri_max_fwd = 0;
 };
 
+// Views of the loaded scope.
+inline View make_view(const DevCsr* a, const DevCsr* b) {
+    View v{};
+    v.off0 = a->off; v.adj0 = a->adj; v.w0 = a->w;
+    if (b) { v.off1 = b->off; v.adj1 = b->adj; v.w1 = b->w; v.nlists = 2; }
+    else { v.off1 = a->off; v.adj1 = a->adj; v.w1 = a->w; v.nlists = 1; }
+    return v;
+}
+inline View pull_view(const DevGraph& g, int scope) {
+    if (scope == TGO_SCOPE_IN_E) return make_view(&g.out, nullptr);
+    if (scope == TGO_SCOPE_OUT_E) return make_view(&g.in, nullptr);
+    return make_view(&g.out, &g.in);
+}
+inline View push_view(const DevGraph& g, int scope) {
+    if (g.has_transpose) return make_view(&g.push_t, nullptr);
+    if (scope == TGO_SCOPE_IN_E) return make_view(&g.in, nullptr);
+    if (scope == TGO_SCOPE_OUT_E) return make_view(&g.out, nullptr);
+    return make_view(&g.out, &g.in);
+}
+
 // Multi-source BFS levels as bit planes: the level of (v, source r) is
 // sum_k ((p[k * stride + v] >> r) & 1) << k; levels < 2^kLevelPlanes (uint16 range).
 constexpr int kLevelPlanes = 16;
@@ -506,7 +527,7 @@ constexpr int kDsCountShift = 35;   // queue counters: count << 35 | entries (on
                                     // counts < 2^29 (a queue holds <= 2n + 2 takes: n <= 2^28 - 1),
                                     // entries < 2^35 (RMAT-27 bothE: 2^32)
 static_assert((int64_t(1) << (64 - kDsCountShift)) > 2 * (int64_t(1) << 27) + 2,
-              "the device delta loop must hold a scale-27 queue (api.cpp run_delta_split guard)");
+              "the device delta loop must hold a scale-27 queue (api_traverse.cpp run_delta_split guard)");
 // Binned form (kDsMaxBins piles): a relaxation that improves a vertex to a distance of a later
 // bucket appends it to that bucket's pile; the next bucket is extracted from its pile, not by
 // a scan of the whole pending bitmap (delta_loop.hip).

@@ -471,7 +471,7 @@ static void relabel_by_degree(HostGraph& g, int threads) {
     auto t1 = std::chrono::steady_clock::now();
     const int32_t* p = g.perm.data();
     permute_graph(g, [p](int32_t u) { return p[u]; }, threads);
-    if (std::getenv("TGO_TRACE") && std::atoi(std::getenv("TGO_TRACE")))
+    if (trace_on())
         std::fprintf(stderr, "[tgo] relabel: order %.1f ms, permute %.1f ms\n",
                      std::chrono::duration<double, std::milli>(t1 - t0).count(),
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
@@ -580,7 +580,7 @@ static void fold_representatives(RowStaging& st, HostGraph& g) {
 struct PhaseClock {
     bool on;
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    PhaseClock() : on(std::getenv("TGO_TRACE") && std::atoi(std::getenv("TGO_TRACE")) != 0) {}
+    PhaseClock() : on(trace_on()) {}
     void lap(const char* what) {
         if (!on) return;
         const auto now = std::chrono::steady_clock::now();

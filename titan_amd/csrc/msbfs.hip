@@ -1099,16 +1099,16 @@ hipError_t k_ms_pull(const View& pull, const View& push, int64_t n_active, uint6
     // TGO_MS_STEP: entries a lane loads per round trip of its own list (4 default since the
     // trips are branch-free, round 6: sweep 3.623 -> 3.562 ms against 8 with the branchy trips,
     // profiles/r06ms1_ms_branchfree_ab.log; 8 / 16 probes)
-    static const int step = [] { const char* e = std::getenv("TGO_MS_STEP"); return e ? std::atoi(e) : 4; }();
-    static const bool diag = [] { const char* e = std::getenv("TGO_MS_DIAG"); return e && std::atoi(e) != 0; }();
+    static const int step = static_cast<int>(env_i64("TGO_MS_STEP", 4));
+    static const bool diag = env_i64("TGO_MS_DIAG", 0) != 0;
     // TGO_MS_LONG: entries per lane per trip of a long list.  1 (default, round 4): with the
     // source split most long walks stop early, and a 64-entry trip stops them soonest — sweep
     // 4.27 -> 3.69-3.74 ms against 4 (2: 4.00, 8: 4.60; profiles/r04z4_ms_pull_ab.log)
-    static const int lng = [] { const char* e = std::getenv("TGO_MS_LONG"); return e ? std::atoi(e) : 1; }();
+    static const int lng = static_cast<int>(env_i64("TGO_MS_LONG", 1));
     // TGO_MS_RAMP=1 (with TGO_MS_LONG=4): a long list's first trip reads 64 entries
-    static const bool ramp = [] { const char* e = std::getenv("TGO_MS_RAMP"); return e && std::atoi(e) != 0; }();
+    static const bool ramp = env_i64("TGO_MS_RAMP", 0) != 0;
     // TGO_MS_COOP: lists longer than this are walked by the whole wave (64 default)
-    static const int64_t coop = [] { const char* e = std::getenv("TGO_MS_COOP"); return e ? std::atoll(e) : kCoop; }();
+    static const int64_t coop = env_i64("TGO_MS_COOP", kCoop);
     const dim3 grid(grid_for(n_active, 8192));
 #define TGO_MS_PULL(S, D, LG, R) ms_pull<S, D, LG, R><<<grid, kBlock, 0, s>>>(pull, push, n_active, full, fr, fbm, vis, \
         nx, lvl, cnt, next_level, filter_from, dense, cand, cs, coop, count_open, head)
@@ -1189,7 +1189,7 @@ hipError_t k_ms_queue(const View& push, int64_t n_active, const uint64_t* fr, in
 hipError_t k_ms_push(const View& push, const int32_t* q, const int64_t* qpre, int64_t qlen, const uint64_t* fr,
                      const uint64_t* vis, uint64_t* nx, hipStream_t s, PackTouch touch, uint64_t mask, bool probe,
                      uint64_t* own_nx, int64_t own_lo) {
-    static const bool e8 = [] { const char* e = std::getenv("TGO_MS_PUSH_E"); return e && std::atoi(e) == 8; }();
+    static const bool e8 = env_i64("TGO_MS_PUSH_E", 0) == 8;
     if (e8) ms_push<8><<<256 * 8, kBlock, 0, s>>>(push, q, qpre, qlen, fr, vis, nx, touch, mask, probe, own_nx, own_lo,
                                                   nullptr, nullptr);
     else ms_push<><<<256 * 8, kBlock, 0, s>>>(push, q, qpre, qlen, fr, vis, nx, touch, mask, probe, own_nx, own_lo,

@@ -27,9 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
-#include "engine.hpp"
-#include "trace.hpp"
-#include "../../include/titan_gpu_olap_part.h"
+#include "ctx.hpp"
 
 // Exchange: the four collectives the sweep needs, all on device buffers, ordered on `s`.
 struct tgo_exchange {
@@ -306,41 +304,7 @@ const char* tgo_exchange_last_error(const tgo_exchange* x) { return x ? x->err.c
 
 namespace tgo {
 
-// ctx accessors (api.cpp): the ctx stream, partition dimensions, error text
-hipStream_t part_stream(tgo_ctx* ctx);
-int part_dims(tgo_ctx* ctx, int64_t* n_local, int64_t* lo, int64_t* n_global, int64_t* entries);
-int part_fail(tgo_ctx* ctx, int code, const std::string& msg);
-int part_scratch(tgo_ctx* ctx, void** p, int64_t bytes, int slot);
-int64_t* part_dcounts_of(tgo_ctx* ctx);
-// this rank's slice of the candidate words bypasses the pack / exchange (ORed in directly by the
-// settle); (nullptr, -1) turns it off
-void part_ms_bypass(tgo_ctx* ctx, uint64_t* cand_global, int self);
-// the next settle sums its new frontier's push entries per source into out (one-shot)
-int part_ms_settle_sums(tgo_ctx* ctx, int64_t* out, bool count_only = false);
-// the next push writes its owned targets straight into next (bypass on); nullptr cancels
-void part_ms_own_next(tgo_ctx* ctx, uint64_t* next);
-// device words to the host through the mapped counter page (no stream synchronisation)
-int part_read_words(tgo_ctx* ctx, const int64_t* dev, int count, int64_t* out);
-int part_sssp_relax_dev(tgo_ctx* ctx, int64_t thr, int32_t nranks, int64_t* send, int64_t* sizes);
-int part_sssp_header_fold(tgo_ctx* ctx, const int64_t* own, const int64_t* recv, int nranks, int64_t* out);
-int part_sssp_split(tgo_ctx* ctx, int64_t delta, bool* on);
-bool part_sssp_devloop(const tgo_ctx* ctx);
-int part_sssp_dev_relax(tgo_ctx* ctx, int32_t nranks, int64_t* send, int64_t* sizes, int64_t* fold);
-int part_sssp_header_read(tgo_ctx* ctx, const int64_t* own, const int64_t* recv, int nranks, int64_t* out,
-                          int64_t* words);
-int part_sssp_dev_apply(tgo_ctx* ctx, const int64_t* recv, int64_t npairs);
-int part_sssp_dev_extract(tgo_ctx* ctx, int64_t thr);
-double ms_split_of(const tgo_ctx* ctx);
-std::shared_ptr<void>& part_state_of(tgo_ctx* ctx);
-int part_in_list(tgo_ctx* ctx, const int32_t** adj, int64_t* nnz);
-int part_out_list(tgo_ctx* ctx, const int32_t** adj, int64_t* nnz);
-bool ms_ghost_of(const tgo_ctx* ctx);
-int part_pr_layout_of(tgo_ctx* ctx, int32_t* world, int64_t* hot, int64_t* span);
-int part_upload(tgo_ctx* ctx, HostGraph& h, int64_t n_global, int64_t lo);
-int part_rows_take(tgo_ctx* ctx, RowStaging& st, std::string& err);
-void part_drop_staging(tgo_ctx* ctx);
-int part_threads(const tgo_ctx* ctx);
-void part_set_live(tgo_ctx* ctx, int64_t live);
+// part_scratch (api.cpp) for an array of `count` T
 template <class T>
 int scratch(tgo_ctx* ctx, T*& p, int64_t count, int slot) {
     void* q = nullptr;
@@ -362,8 +326,8 @@ struct Driver {
     hipStream_t st;
     int64_t* dbuf = nullptr;        // device scalars (8)
     int64_t* hc = nullptr;          // pinned host view
-    int xfail(int code) { return part_fail(ctx, code, "exchange: " + x->err); }
-    int hip(const char* what) { return part_fail(ctx, TGO_E_HIP, what); }
+    int xfail(int code) { return fail(ctx, code, "exchange: " + x->err); }
+    int hip(const char* what) { return fail(ctx, TGO_E_HIP, what); }
     // out[i] = op over the ranks of vals[i], i < k <= 8 (one round trip)
     int reduce(const int64_t* vals, int k, int op, int64_t* out) {
         for (int i = 0; i < k; ++i) hc[i] = vals[i];
@@ -378,13 +342,13 @@ int driver_open(tgo_ctx* ctx, tgo_exchange* x, const char* name, int slot, Drive
     int rc = part_dims(ctx, &nl, &lo, &ng, &ent);
     if (rc) return rc;
     if (static_cast<int64_t>(x->world) * nl != ng || lo != static_cast<int64_t>(x->rank) * nl)
-        return part_fail(ctx, TGO_E_INVALID, std::string(name) + ": the exchange's world / rank do not match the partition");
+        return fail(ctx, TGO_E_INVALID, std::string(name) + ": the exchange's world / rank do not match the partition");
     d.ctx = ctx;
     d.x = x;
-    d.st = part_stream(ctx);
+    d.st = ctx->stream;
     if ((rc = scratch(ctx, d.dbuf, 8, slot))) return rc;
     d.hc = x->host_counts();
-    if (!d.hc) return part_fail(ctx, TGO_E_HIP, std::string(name) + ": pinned counts");
+    if (!d.hc) return fail(ctx, TGO_E_HIP, std::string(name) + ": pinned counts");
     return TGO_OK;
 }
 
@@ -424,7 +388,7 @@ int build_ghost(tgo_ctx* ctx, tgo_exchange* x, Driver& d, int64_t nl, int64_t ho
     std::string err;
     int32_t* need = nullptr;
     std::vector<int64_t> need_count;
-    if ((rc = ghost_needs(adj, nnz, adj2, nnz2, nl, R, W, &need, need_count, st, err))) return part_fail(ctx, rc, err);
+    if ((rc = ghost_needs(adj, nnz, adj2, nnz2, nl, R, W, &need, need_count, st, err))) return fail(ctx, rc, err);
     struct Free { void* p; ~Free() { if (p) (void)hipFree(p); } } free_need{need};
     int64_t nneed = 0;
     for (int64_t c : need_count) nneed += c;
@@ -447,7 +411,7 @@ int build_ghost(tgo_ctx* ctx, tgo_exchange* x, Driver& d, int64_t nl, int64_t ho
         hipMalloc(&gh.recv_pos, std::max<int64_t>(nneed, 1) * 4) != hipSuccess ||
         hipMalloc(&gh.sbuf, std::max<int64_t>(ngive, 1) * 8) != hipSuccess ||
         hipMalloc(&gh.rbuf, std::max<int64_t>(nneed, 1) * 8) != hipSuccess)
-        return part_fail(ctx, TGO_E_OOM, "ghost buffers");
+        return fail(ctx, TGO_E_OOM, "ghost buffers");
     std::vector<size_t> ib(W), io(W), gb(W), go(W);
     gh.sb.assign(W, 0); gh.so.assign(W, 0); gh.rb.assign(W, 0); gh.ro.assign(W, 0);
     size_t a = 0, b = 0;
@@ -459,19 +423,19 @@ int build_ghost(tgo_ctx* ctx, tgo_exchange* x, Driver& d, int64_t nl, int64_t ho
     }
     if (int r = x->all_to_allv(need, ib.data(), io.data(), gh.send_row, gb.data(), go.data(), st)) return d.xfail(r);
     if (hipError_t e = k_sub_i32(gh.send_row, ngive, static_cast<int32_t>(static_cast<int64_t>(R) * nl), st))
-        return part_fail(ctx, TGO_E_HIP, hipGetErrorString(e));
+        return fail(ctx, TGO_E_HIP, hipGetErrorString(e));
     if (hipError_t e = k_gathered_pos(need, nneed, nl, span, hot, W, gh.recv_pos, st))
-        return part_fail(ctx, TGO_E_HIP, hipGetErrorString(e));
+        return fail(ctx, TGO_E_HIP, hipGetErrorString(e));
     if (hipStreamSynchronize(st) != hipSuccess) return d.hip("ghost lists");
     return TGO_OK;
 }
 
-// the ghost lists a driver keeps with the graph (part_state_of): PageRank's and the sweep's
+// the ghost lists a driver keeps with the graph (tgo_ctx::part_state): PageRank's and the sweep's
 struct GhostCache {
     std::shared_ptr<PrGhost> pr, ms;
 };
 GhostCache& ghost_cache(tgo_ctx* ctx) {
-    std::shared_ptr<void>& st = part_state_of(ctx);
+    std::shared_ptr<void>& st = ctx->part_state;
     if (!st) st = std::make_shared<GhostCache>();
     return *static_cast<GhostCache*>(st.get());
 }
@@ -483,15 +447,15 @@ extern "C" int tgo_part_msbfs_run(tgo_ctx* ctx, tgo_exchange* x, const int64_t* 
                                   int32_t* levels_out) {
     if (!ctx) return TGO_E_INVALID;
     if (!x || !seeds || nseeds < 1 || nseeds > TGO_MAX_SOURCES || max_depth < 0)
-        return part_fail(ctx, TGO_E_INVALID, "tgo_part_msbfs_run: bad arguments");
+        return fail(ctx, TGO_E_INVALID, "tgo_part_msbfs_run: bad arguments");
     int64_t nl = 0, lo = 0, ng = 0, ent = 0;
     int rc = part_dims(ctx, &nl, &lo, &ng, &ent);
     if (rc) return rc;
     const int W = x->world;
     if (static_cast<int64_t>(W) * nl != ng || lo != static_cast<int64_t>(x->rank) * nl)
-        return part_fail(ctx, TGO_E_INVALID, "tgo_part_msbfs_run: the exchange's world / rank do not match the partition");
-    hipStream_t st = part_stream(ctx);
-    auto xfail = [&](int code) { return part_fail(ctx, code, "exchange: " + x->err); };
+        return fail(ctx, TGO_E_INVALID, "tgo_part_msbfs_run: the exchange's world / rank do not match the partition");
+    hipStream_t st = ctx->stream;
+    auto xfail = [&](int code) { return fail(ctx, code, "exchange: " + x->err); };
     // scratch (ctx-owned, reused): two alternating global mask buffers, the candidate masks,
     // the pair buffers, the device counts and the split sizes
     uint64_t *g0 = nullptr, *g1 = nullptr, *cand = nullptr;
@@ -501,7 +465,7 @@ extern "C" int tgo_part_msbfs_run(tgo_ctx* ctx, tgo_exchange* x, const int64_t* 
         (rc = scratch(ctx, send, pairs_cap, 3)) || (rc = scratch(ctx, recv, pairs_cap, 4)) ||
         (rc = scratch(ctx, dc, 3 + 2 * TGO_MAX_SOURCES, 5)) || (rc = scratch(ctx, sizes, 2 * W, 6)))
         return rc;
-    int64_t* const caller_dc = part_dcounts_of(ctx);       // restored at the end
+    int64_t* const caller_dc = ctx->part_dcounts;       // restored at the end
     // the rank's own candidate words never travel: the packs skip its slice and the settles OR
     // it in (the Python reference driver keeps packing every slice)
     struct Bypass {
@@ -520,11 +484,11 @@ extern "C" int tgo_part_msbfs_run(tgo_ctx* ctx, tgo_exchange* x, const int64_t* 
         (void)hipMemsetAsync(cand, 0, ng * 8, st);
     };
     int64_t* hc = x->host_counts();                         // pinned host view of the counts (kept)
-    if (!hc) return part_fail(ctx, TGO_E_HIP, "tgo_part_msbfs_run: pinned counts");
+    if (!hc) return fail(ctx, TGO_E_HIP, "tgo_part_msbfs_run: pinned counts");
     // dense levels: the ghost exchange (only the masks this rank's lists read, lists built once
     // per graph) unless TGO_TUNE_MS_GHOST = 0 or a single rank
     PrGhost* gh = nullptr;
-    if (W > 1 && ms_ghost_of(ctx)) {
+    if (W > 1 && ctx->ms_ghost != 0) {
         Driver d{ctx, x, st, dc, hc};
         std::shared_ptr<PrGhost>& cached = ghost_cache(ctx).ms;
         gh = cached.get();
@@ -539,11 +503,11 @@ extern "C" int tgo_part_msbfs_run(tgo_ctx* ctx, tgo_exchange* x, const int64_t* 
     auto global2 = [&](int64_t a, int64_t b, int64_t* out) -> int {
         hc[0] = a; hc[1] = b;
         if (hipMemcpyAsync(dc, hc, 2 * sizeof(int64_t), hipMemcpyHostToDevice, st) != hipSuccess)
-            return part_fail(ctx, TGO_E_HIP, "counts upload");
+            return fail(ctx, TGO_E_HIP, "counts upload");
         if (int r = x->all_reduce_sum(dc, 2, st)) return xfail(r);
         if (hipMemcpyAsync(hc, dc, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess)
-            return part_fail(ctx, TGO_E_HIP, "counts read");
+            return fail(ctx, TGO_E_HIP, "counts read");
         out[0] = hc[0]; out[1] = hc[1];
         return TGO_OK;
     };
@@ -568,7 +532,7 @@ extern "C" int tgo_part_msbfs_run(tgo_ctx* ctx, tgo_exchange* x, const int64_t* 
         if (int r = x->all_reduce_sum(sc64, 64, st)) return xfail(r);
         if (hipMemcpyAsync(host, sc64, 64 * sizeof(int64_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess)
-            return part_fail(ctx, TGO_E_HIP, "per-source sums read");
+            return fail(ctx, TGO_E_HIP, "per-source sums read");
         return TGO_OK;
     };
     // pack + exchange the candidate masks of a push (fixed slots when cap bounds them), then
@@ -590,7 +554,7 @@ extern "C" int tgo_part_msbfs_run(tgo_ctx* ctx, tgo_exchange* x, const int64_t* 
             for (int p = 0; p < W; ++p) so[p] = static_cast<size_t>(p) * slot;
             sb[x->rank] = 0;
             if (hipMemsetAsync(reinterpret_cast<char*>(recv) + so[x->rank], 0, 16, st) != hipSuccess)
-                return part_fail(ctx, TGO_E_HIP, "own slot header");
+                return fail(ctx, TGO_E_HIP, "own slot header");
             if (int r = x->all_to_allv(send, sb.data(), so.data(), recv, sb.data(), so.data(), st)) return xfail(r);
             return fixed_fn(cap);
         }
@@ -599,7 +563,7 @@ extern "C" int tgo_part_msbfs_run(tgo_ctx* ctx, tgo_exchange* x, const int64_t* 
         if (int r = x->all_to_all(sizes, sizes + W, 8, st)) return xfail(r);
         std::vector<int64_t> both(2 * W);
         if (hipMemcpyAsync(both.data(), sizes, 2 * W * sizeof(int64_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) return part_fail(ctx, TGO_E_HIP, "split sizes read");
+            hipStreamSynchronize(st) != hipSuccess) return fail(ctx, TGO_E_HIP, "split sizes read");
         std::vector<size_t> sb(W), so(W), rb(W), ro(W);
         std::vector<int64_t> rpairs(W);
         size_t a = 0, b = 0;
@@ -652,7 +616,7 @@ extern "C" int tgo_part_msbfs_run(tgo_ctx* ctx, tgo_exchange* x, const int64_t* 
             if (gh) {                                   // ghosts: pack -> all-to-allv -> unpack into glob[0]
                 const uint64_t* own = glob[0] + lo;
                 if (k_pack_u64(own, gh->send_row, gh->nsend, reinterpret_cast<uint64_t*>(gh->sbuf), st) != hipSuccess) {
-                    rc = part_fail(ctx, TGO_E_HIP, "ghost pack");
+                    rc = fail(ctx, TGO_E_HIP, "ghost pack");
                     break;
                 }
                 if (int r = x->all_to_allv(gh->sbuf, gh->sb.data(), gh->so.data(), gh->rbuf, gh->rb.data(), gh->ro.data(), st)) {
@@ -661,7 +625,7 @@ extern "C" int tgo_part_msbfs_run(tgo_ctx* ctx, tgo_exchange* x, const int64_t* 
                 }
                 if (k_unpack_u64(reinterpret_cast<const uint64_t*>(gh->rbuf), gh->recv_pos, gh->nrecv, glob[0], st) !=
                     hipSuccess) {
-                    rc = part_fail(ctx, TGO_E_HIP, "ghost unpack");
+                    rc = fail(ctx, TGO_E_HIP, "ghost unpack");
                     break;
                 }
             } else if (int r = x->all_gather(glob[0], static_cast<size_t>(nl) * 8, st)) {
@@ -712,11 +676,11 @@ extern "C" int tgo_part_msbfs_run(tgo_ctx* ctx, tgo_exchange* x, const int64_t* 
         std::copy(e.begin(), e.end(), both.begin() + nseeds);
         int64_t* d = dc + 3;
         if (hipMemcpyAsync(d, both.data(), both.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess)
-            return part_fail(ctx, TGO_E_HIP, "stats upload");
+            return fail(ctx, TGO_E_HIP, "stats upload");
         if (int q = x->all_reduce_sum(d, both.size(), st)) return xfail(q);
         if (hipMemcpyAsync(both.data(), d, both.size() * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess)
-            return part_fail(ctx, TGO_E_HIP, "stats read");
+            return fail(ctx, TGO_E_HIP, "stats read");
         for (int i = 0; i < nseeds; ++i) {
             if (reached) reached[i] = both[i];
             if (entries) entries[i] = both[nseeds + i];
@@ -739,7 +703,7 @@ extern "C" int tgo_part_bfs_run(tgo_ctx* ctx, tgo_exchange* x, int64_t seed_glob
                                 double beta, int64_t* dist_local, int64_t* reached, int32_t* levels_out) {
     if (!ctx) return TGO_E_INVALID;
     if (!x || max_depth < 0 || !(alpha > 0.0) || !(beta > 0.0))
-        return part_fail(ctx, TGO_E_INVALID, "tgo_part_bfs_run: bad arguments");
+        return fail(ctx, TGO_E_INVALID, "tgo_part_bfs_run: bad arguments");
     Driver d{};
     int64_t nl = 0, lo = 0, ng = 0, ent = 0;
     int rc = driver_open(ctx, x, "tgo_part_bfs_run", 12, d, nl, lo, ng, ent);
@@ -755,7 +719,7 @@ extern "C" int tgo_part_bfs_run(tgo_ctx* ctx, tgo_exchange* x, int64_t seed_glob
     if ((rc = scratch(ctx, f0, nwg, 8)) || (rc = scratch(ctx, f1, nwg, 9)) || (rc = scratch(ctx, disc, nwg, 10)) ||
         (rc = scratch(ctx, recv, nwg, 11)) || (rc = scratch(ctx, dc, 4, 13)))
         return rc;
-    int64_t* const caller_dc = part_dcounts_of(ctx);
+    int64_t* const caller_dc = ctx->part_dcounts;
     uint64_t* glob[2] = {f0, f1};
     int64_t c[2] = {0, 0};
     if ((rc = tgo_part_bfs_begin(ctx, seed_global, glob[0] + x->rank * nwl, c))) return rc;
@@ -811,7 +775,7 @@ extern "C" int tgo_part_bfs_run(tgo_ctx* ctx, tgo_exchange* x, int64_t seed_glob
 extern "C" int tgo_part_sssp_run(tgo_ctx* ctx, tgo_exchange* x, int64_t seed_global, int64_t delta, int64_t* dist_local,
                                  int64_t* reached, int32_t* phases_out) {
     if (!ctx) return TGO_E_INVALID;
-    if (!x) return part_fail(ctx, TGO_E_INVALID, "tgo_part_sssp_run: bad arguments");
+    if (!x) return fail(ctx, TGO_E_INVALID, "tgo_part_sssp_run: bad arguments");
     Driver d{};
     int64_t nl = 0, lo = 0, ng = 0, ent = 0;
     int rc = driver_open(ctx, x, "tgo_part_sssp_run", 17, d, nl, lo, ng, ent);
@@ -826,20 +790,20 @@ extern "C" int tgo_part_sssp_run(tgo_ctx* ctx, tgo_exchange* x, int64_t seed_glo
     int64_t wmin = 0, gmin = 0;
     if ((rc = tgo_part_weight_min(ctx, &wmin))) return rc;
     if ((rc = d.reduce(&wmin, 1, tgo_exchange::kRedMin, &gmin))) return rc;
-    if (gmin < 0) return part_fail(ctx, TGO_E_INVALID, "delta-stepping needs non-negative weights (a rank holds a negative weight)");
+    if (gmin < 0) return fail(ctx, TGO_E_INVALID, "delta-stepping needs non-negative weights (a rank holds a negative weight)");
     int64_t out[2] = {0, 0};
     if ((rc = tgo_part_sssp_begin(ctx, seed_global, delta, out))) return rc;
     if (delta <= 0) {           // the ranks' default widths follow their local mean weight: agree on one
         if ((rc = d.reduce(&out[1], 1, tgo_exchange::kRedMax, &delta))) return rc;
     }
-    if (delta <= 0) return part_fail(ctx, TGO_E_INVALID, "tgo_part_sssp_run: bucket width");
+    if (delta <= 0) return fail(ctx, TGO_E_INVALID, "tgo_part_sssp_run: bucket width");
     // light/heavy split (weighted loads): the same decision on every rank (the load's weights
     // and the agreed width); the loop below is the same either way
     bool split = false;
     if ((rc = part_sssp_split(ctx, delta, &split))) return rc;
     (void)split;
     // on the device-sized loop (delta_loop.hip) nothing but the header comes to the host
-    const bool dev = part_sssp_devloop(ctx);
+    const bool dev = ctx->part_devloop;
     int64_t thr = delta;
     int phases = 0;
     // per phase, ONE host read: the relax writes a 4-word header per peer on the device
@@ -903,7 +867,7 @@ extern "C" int tgo_part_pagerank_run(tgo_ctx* ctx, tgo_exchange* x, const tgo_pr
                                      double* pr_local, int64_t* exchanged_bytes) {
     if (!ctx) return TGO_E_INVALID;
     if (!x || !args || args->max_iterations < 1 || exchange_mode < 0 || exchange_mode > 1)
-        return part_fail(ctx, TGO_E_INVALID, "tgo_part_pagerank_run: bad arguments");
+        return fail(ctx, TGO_E_INVALID, "tgo_part_pagerank_run: bad arguments");
     Driver d{};
     int64_t nl = 0, lo = 0, ng = 0, ent = 0;
     int rc = driver_open(ctx, x, "tgo_part_pagerank_run", 22, d, nl, lo, ng, ent);
@@ -1013,10 +977,10 @@ struct DevTmp {                 // a device temporary of the load (the ctx holds
 static int finish_partition_rows(tgo_ctx* ctx, tgo_exchange* x, int32_t layout, int64_t* part_out, int local_rc,
                                  const std::string& local_err) {
     const int W = x->world, R = x->rank;
-    hipStream_t st = part_stream(ctx);
+    hipStream_t st = ctx->stream;
     std::string err = local_err;
-    auto xerr = [&](int code) { return part_fail(ctx, code, "exchange: " + x->err); };
-    auto hip = [&](const char* what) { x->abort(); return part_fail(ctx, TGO_E_HIP, std::string("tgo_finish_partition_rows: ") + what); };
+    auto xerr = [&](int code) { return fail(ctx, code, "exchange: " + x->err); };
+    auto hip = [&](const char* what) { x->abort(); return fail(ctx, TGO_E_HIP, std::string("tgo_finish_partition_rows: ") + what); };
     DevTmp red;
     if (red.alloc(8 * sizeof(int64_t)) != hipSuccess) return hip("scratch");
     // element-wise reduction of k host words over the ranks
@@ -1039,8 +1003,8 @@ static int finish_partition_rows(tgo_ctx* ctx, tgo_exchange* x, int32_t layout, 
     int64_t v1[4] = {drc ? 1 : 0, count, staged ? stg.opts.scope + 1 : 0, staged && stg.opts.weight_key != 0 ? 1 : 0};
     const int64_t own_scope = v1[2], own_weighted = v1[3];
     if (int rc = reduce(v1, 4, tgo_exchange::kRedMax)) return rc;
-    if (drc) return part_fail(ctx, drc, "tgo_finish_partition_rows: " + err);
-    if (v1[0]) return part_fail(ctx, TGO_E_INVALID, "tgo_finish_partition_rows: another rank failed to decode its rows");
+    if (drc) return fail(ctx, drc, "tgo_finish_partition_rows: " + err);
+    if (v1[0]) return fail(ctx, TGO_E_INVALID, "tgo_finish_partition_rows: another rank failed to decode its rows");
     if (!staged) {
         stg.opts.scope = static_cast<int32_t>(std::max<int64_t>(0, v1[2] - 1));
         stg.opts.weight_key = v1[3];
@@ -1049,7 +1013,7 @@ static int finish_partition_rows(tgo_ctx* ctx, tgo_exchange* x, int32_t layout, 
     int mismatch = staged && (own_scope != v1[2] || own_weighted != v1[3]);
     const int64_t S = std::max<int64_t>(64, (v1[1] + 63) / 64 * 64), lo = static_cast<int64_t>(R) * S;
     const int64_t n_global = static_cast<int64_t>(W) * S;
-    if (n_global >= INT32_MAX) return part_fail(ctx, TGO_E_UNSUPPORTED, "tgo_finish_partition_rows: more than 2^31 - 1 slots");
+    if (n_global >= INT32_MAX) return fail(ctx, TGO_E_UNSUPPORTED, "tgo_finish_partition_rows: more than 2^31 - 1 slots");
     // 2. the global id map: every rank's live ids at their slots
     std::vector<int64_t> slot_vid(static_cast<size_t>(n_global));
     {
@@ -1066,7 +1030,7 @@ static int finish_partition_rows(tgo_ctx* ctx, tgo_exchange* x, int32_t layout, 
             return hip("id read");
     }
     HostGraph h;
-    const int threads = part_threads(ctx);
+    const int threads = threads_of(ctx);
     int arc = assemble_partition_rows(stg, slot_vid, S, R, h, threads, err);
     if (!arc && mismatch) {
         err = "the ranks staged rows with different scopes or weight keys";
@@ -1094,8 +1058,8 @@ static int finish_partition_rows(tgo_ctx* ctx, tgo_exchange* x, int32_t layout, 
     //    on failure before the graph replaces the ctx's)
     int64_t v4[3] = {arc ? 1 : 0, h.truncated, count};
     if (int rc = reduce(v4, 3, tgo_exchange::kRedSum)) return rc;
-    if (arc) return part_fail(ctx, arc, "tgo_finish_partition_rows: " + err);
-    if (v4[0]) return part_fail(ctx, TGO_E_INVALID, "tgo_finish_partition_rows: another rank failed to assemble its rows");
+    if (arc) return fail(ctx, arc, "tgo_finish_partition_rows: " + err);
+    if (v4[0]) return fail(ctx, TGO_E_INVALID, "tgo_finish_partition_rows: another rank failed to assemble its rows");
     if (v4[1] > 0 && h.scope != TGO_SCOPE_BOTH_E) {
         std::vector<int64_t> cnt, pairs;
         partition_pull_pairs(h, lo, S, W, cnt, pairs);
@@ -1123,7 +1087,7 @@ static int finish_partition_rows(tgo_ctx* ctx, tgo_exchange* x, int32_t layout, 
         partition_push_from_pairs(h, recv.data(), static_cast<int64_t>(b / 16));
     }
     if (int rc = part_upload(ctx, h, n_global, lo)) return rc;
-    part_set_live(ctx, count);
+    ctx->st.num_vertices = count;
     part_out[0] = count;
     part_out[1] = S;
     part_out[2] = v4[2];
@@ -1133,7 +1097,7 @@ static int finish_partition_rows(tgo_ctx* ctx, tgo_exchange* x, int32_t layout, 
 extern "C" int tgo_finish_partition_rows(tgo_ctx* ctx, tgo_exchange* x, int32_t layout, int64_t* part) {
     if (!ctx) return TGO_E_INVALID;
     if (!x || !part || x->world < 1 || x->rank < 0 || x->rank >= x->world)
-        return part_fail(ctx, TGO_E_INVALID, "tgo_finish_partition_rows: bad arguments");
+        return fail(ctx, TGO_E_INVALID, "tgo_finish_partition_rows: bad arguments");
     return finish_partition_rows(ctx, x, layout, part, TGO_OK, std::string());
 }
 
@@ -1141,7 +1105,7 @@ extern "C" int tgo_load_partition_rows(tgo_ctx* ctx, tgo_exchange* x, const tgo_
                                        const tgo_load_opts* opts, int32_t layout, int64_t* part) {
     if (!ctx) return TGO_E_INVALID;
     if (!x || !part || x->world < 1 || x->rank < 0 || x->rank >= x->world)
-        return part_fail(ctx, TGO_E_INVALID, "tgo_load_partition_rows: bad arguments");
+        return fail(ctx, TGO_E_INVALID, "tgo_load_partition_rows: bad arguments");
     const int rc = tgo_load_rows(ctx, rows, schema, opts);
     return finish_partition_rows(ctx, x, layout, part, rc, rc ? std::string(tgo_last_error(ctx)) : std::string());
 }

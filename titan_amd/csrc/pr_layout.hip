@@ -321,7 +321,7 @@ int build_cold_blocks_device(const int64_t* d_off, const int32_t* d_adj, int64_t
     if (win < 0 || win > 65536 || win > hot) win = 0;       // uint16 window entries inside the hot range
     const int64_t nseg = (n_src - hot + seg - 1) / seg;
     Sort so{{}, 0, s};
-    static const bool trace = std::getenv("TGO_TRACE") && std::atoi(std::getenv("TGO_TRACE")) != 0;
+    static const bool trace = trace_on();
     auto t_last = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
         if (!trace && !tracing()) return;

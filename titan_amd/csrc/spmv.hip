@@ -1076,15 +1076,13 @@ static FxGuard fx_guard(const ColdBlocks& cb) {
 // Cold phase: the cold segments' partial sums, folded per row into csum (reads only the cold
 // sources [hot, n_src) of `contrib`).
 static bool fx_fold_in_hot() {                       // TGO_PR_FX_FOLD (read per launch, A/B)
-    const char* e = std::getenv("TGO_PR_FX_FOLD");
-    return e ? std::atoi(e) != 0 : true;
+    return env_i64("TGO_PR_FX_FOLD", 1) != 0;
 }
 static int fx_diag() {                                // read per launch: an A/B flips it between runs
-    const char* e = std::getenv("TGO_PR_FX_DIAG");
-    return e ? std::atoi(e) : 0;
+    return static_cast<int>(env_i64("TGO_PR_FX_DIAG", 0));
 }
 static bool row_prefetch() {
-    static const bool on = [] { const char* e = std::getenv("TGO_PR_PF"); return !e || std::atoi(e) != 0; }();
+    static const bool on = env_i64("TGO_PR_PF", 1) != 0;
     return on;
 }
 // dynamic LDS past 64 KB, raised once per kernel instantiation
@@ -1259,7 +1257,7 @@ hipError_t k_pr_hot_phase(const ColdBlocks& cb, const double* contrib, const dou
         else
             gather_hot_big<16384, 1024, 14><<<g, 1024, 0, s>>>(cb.hcsr.off, padj, rb.bdesc, contrib, fin);
     } else if (rb.nblocks > 0) {
-        static const int32_t skip_below = static_cast<int32_t>(std::atol(std::getenv("TGO_PR_SKIP_BELOW") ? std::getenv("TGO_PR_SKIP_BELOW") : "0"));
+        static const int32_t skip_below = static_cast<int32_t>(env_i64("TGO_PR_SKIP_BELOW", 0));
         if (skip_below > 0)
             gather_hot_pf<true><<<static_cast<unsigned>(rb.nblocks), kBlock, 0, s>>>(cb.hcsr.off, cb.hcsr.adj, rb.bdesc,
                                                                                       contrib, fin, skip_below);

@@ -22,6 +22,7 @@
 #include <sys/mman.h>
 
 #include <hip/hip_runtime.h>
+#include "env.hpp"
 
 namespace tgo {
 namespace {
@@ -43,7 +44,7 @@ int current_device() {
 // this shows whether an allocation or a device synchronisation is the stall)
 template <class F>
 hipError_t timed(const char* what, size_t bytes, F&& f) {
-    static const bool trace = std::getenv("TGO_TRACE") && std::atoi(std::getenv("TGO_TRACE")) != 0;
+    static const bool trace = trace_on();
     if (!trace) return f();
     const auto t0 = std::chrono::steady_clock::now();
     const hipError_t e = f();

@@ -572,7 +572,7 @@ def _allreduce_counts(c, device, comm):
 
 # Direction switch of the single-source BFS (Beamer): bottom-up once the frontier's entries pass
 # 1/BFS_ALPHA of the unexplored ones, top-down again below n/BFS_BETA frontier vertices — the
-# one-GPU engine's defaults (api.cpp run_bfs, round 5: 30 / 5000 against Beamer's 15 / 18,
+# one-GPU engine's defaults (api_traverse.cpp run_bfs, round 5: 30 / 5000 against Beamer's 15 / 18,
 # profiles/r05ab_bfs_switch_ab.log).
 BFS_ALPHA = 30.0
 BFS_BETA = 5000.0
