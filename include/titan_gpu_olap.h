@@ -363,10 +363,18 @@ int  tgo_copy_multi_distances(tgo_ctx* ctx, int32_t source, int64_t* dist_out);
  * which a row is intersected by its whole wave / staged in LDS and intersected by a whole
  * workgroup (rows too long for LDS stay with the wave); an integer >= 1, < 0 = the default.
  * Same counts for every value (tests use tiny values so that small graphs reach every path). */
+/* TGO_TUNE_CORE_WAVE_ROW (tgo_kcore): a peeled vertex whose neighbourhood holds at least this many
+ * entries is walked by its whole wave instead of its own lane; an integer >= 1.
+ * TGO_TUNE_CORE_TAIL: once at most this many vertices are still unpeeled, one workgroup finishes
+ * the peel inside one launch (at most 4096: larger values mean 4096); 0 = never.
+ * TGO_TUNE_CORE_LDS_QUEUE: the vertices a workgroup's own queue holds, in [1, 4096]: what a
+ * workgroup drops it peels itself from that queue, and only what does not fit goes to the next
+ * launch.  For all three < 0 = the default, and every value gives the same core numbers. */
 enum { TGO_TUNE_MS_SPLIT = 1, TGO_TUNE_MS_GHOST = 2, TGO_TUNE_DS_BINS = 3, TGO_TUNE_DS_PILE_CAP = 4,
        TGO_TUNE_DS_DONE = 5, TGO_TUNE_MS_COLD = 6, TGO_TUNE_DS_PULL = 7, TGO_TUNE_DS_SMALL = 8,
        TGO_TUNE_MS_STAY = 9, TGO_TUNE_MS_SPARSE = 10, TGO_TUNE_TRI_WAVE_ROW = 11,
-       TGO_TUNE_TRI_BLOCK_ROW = 12, TGO_TUNE_MS_HEAD = 13 };
+       TGO_TUNE_TRI_BLOCK_ROW = 12, TGO_TUNE_MS_HEAD = 13, TGO_TUNE_CORE_WAVE_ROW = 14,
+       TGO_TUNE_CORE_TAIL = 15, TGO_TUNE_CORE_LDS_QUEUE = 16 };
 int  tgo_set_tuning(tgo_ctx* ctx, int32_t key, double value);
 
 /* ---- Tracing (the reference's only hook is FulgoraGraphComputer.java:143,307
@@ -433,6 +441,34 @@ typedef struct { int32_t scope; int32_t flags; } tgo_tri_args;
 typedef struct { int64_t triangles, wedges, simple_edges, max_forward; } tgo_tri_info;
 int  tgo_triangles(tgo_ctx* ctx, const tgo_tri_args* args, int64_t* tri_out, tgo_tri_info* info);
 int  tgo_copy_triangles(tgo_ctx* ctx, int64_t* tri_out, int64_t* deg_out, double* lcc_out);
+
+/* ---- k-core decomposition --------------------------------------------------------------
+ * Over the same simple undirected projection as tgo_triangles (u ~ v iff u != v and an OUT or IN
+ * entry of u names v; parallel edges, the two directions of a pair and self-loops collapse; a
+ * vertex cut counts as its canonical vertex).  Per vertex in row order:
+ *   core[v]  the largest k such that v lies in a subgraph of the projection in which every vertex
+ *            has at least k neighbours; 0 for a vertex without entries
+ * The decomposition is unique: results are bit-identical run to run and for every
+ * TGO_TUNE_CORE_* value.  info:
+ *   degeneracy    max core
+ *   innermost     vertices with core == degeneracy
+ *   simple_edges  sum(d) / 2
+ *   levels        distinct core values (0 included when some vertex has none); deterministic;
+ *                 also tgo_stats.iterations
+ *   rounds        peel launches of this run.  A DIAGNOSTIC: it may differ between runs and between
+ *                 tuning values (which workgroup drops a vertex decides whether the next launch or
+ *                 the same one peels it); >= 1 when the projection has an edge
+ * A projection without any edge is not peeled: every core is 0 and info is all zero.
+ * args->scope must be TGO_SCOPE_BOTH_E and the loaded scope (else TGO_E_INVALID), args->flags 0.
+ * Lists that are not each other's transpose (tgo_load_csr with asymmetric rows): TGO_E_UNSUPPORTED;
+ * so does a partitioned ctx.  A failed call leaves the ctx usable.  core_out NULL: the result
+ * stays on the device (tgo_copy_cores; tgo_result_rows kind TGO_RESULT_CORE).  The forward lists
+ * are shared with tgo_triangles; the backward lists (4 bytes per simple edge + 8 (n + 1)) are
+ * built on the first run of a load and stay cached with it (tgo_stats.device_bytes). */
+typedef struct { int32_t scope; int32_t flags; } tgo_core_args;
+typedef struct { int64_t degeneracy, innermost, simple_edges; int32_t levels, rounds; } tgo_core_info;
+int  tgo_kcore(tgo_ctx* ctx, const tgo_core_args* args, int64_t* core_out, tgo_core_info* info);
+int  tgo_copy_cores(tgo_ctx* ctx, int64_t* core_out);
 
 /* ---- Generic vertex programs ----------------------------------------
  * A vertex program the engine does not implement natively runs its execute() on the host
@@ -540,6 +576,8 @@ int  tgo_dense_ids(tgo_ctx* ctx, const int64_t* titan_ids, int64_t count, int64_
  *   TRIANGLES tgo_triangles' count (key_ids[0]: Long; an Integer key when every count is in int
  *             range, else TGO_E_INVALID) and clustering coefficient (key_ids[1]: Double) on every
  *             executed vertex
+ *   CORE      tgo_kcore's core number (Long, or Integer: a core number is at most d(v) < 2^31) on
+ *             every executed vertex; any other typed key: TGO_E_INVALID
  * Compute keys are typed property keys of those datatypes, or generic keys (TGO_DT_OBJECT: what
  * getOrCreatePropertyKey makes for a key the program sets without a schema, DefaultSchemaMaker
  * .java:46-48), whose values carry their class (Long 13, Double 20, Integer 12).  Relation ids are
@@ -548,11 +586,12 @@ int  tgo_dense_ids(tgo_ctx* ctx, const int64_t* titan_ids, int64_t count, int64_
  * nrows keys, nrows+1 entry / byte offsets, nbytes bytes and nentries limit|valuePos words
  * (the tgo_rows layout, so the rows can be scanned again). */
 typedef enum { TGO_RESULT_DISTANCE = 0, TGO_RESULT_PAGERANK = 1, TGO_RESULT_DEGREE = 2,
-               TGO_RESULT_VALUES = 3, TGO_RESULT_COMPONENT = 4, TGO_RESULT_TRIANGLES = 5 } tgo_result_kind;
+               TGO_RESULT_VALUES = 3, TGO_RESULT_COMPONENT = 4, TGO_RESULT_TRIANGLES = 5,
+               TGO_RESULT_CORE = 6 } tgo_result_kind;
 typedef struct {
     int32_t kind;                 /* tgo_result_kind                                          */
     int32_t reserved;             /* TGO_RESULT_VALUES: tgo_value_type of the values           */
-    int64_t key_ids[2];           /* [0] DISTANCE / PAGE_RANK / DEGREE / COMPONENT / TRIANGLES key; [1] OUTGOING_EDGE_COUNT / CLUSTERING */
+    int64_t key_ids[2];           /* [0] DISTANCE / PAGE_RANK / DEGREE / COMPONENT / TRIANGLES / CORE key; [1] OUTGOING_EDGE_COUNT / CLUSTERING */
     int32_t datatypes[2];         /* tgo_datatype of each key                                  */
     int64_t relation_id_base;
 } tgo_result_args;

@@ -302,6 +302,20 @@ JNIEXPORT jlongArray JNICALL JFN(triangles)(JNIEnv* env, jclass cls, jlong h) {
     return distances(env, h, run_triangles, &a);
 }
 
+/* tgo_kcore over the bothE load: every vertex's core number in row order, or NULL on error (the
+ * levels are tgo_stats.iterations afterwards; write-back: tgo_result_rows kind TGO_RESULT_CORE). */
+static int run_kcore(tgo_ctx* c, const void* a, int64_t* o) {
+    return tgo_kcore(c, (const tgo_core_args*)a, o, NULL);
+}
+
+JNIEXPORT jlongArray JNICALL JFN(kcore)(JNIEnv* env, jclass cls, jlong h) {
+    (void)cls;
+    tgo_core_args a;
+    memset(&a, 0, sizeof a);
+    a.scope = TGO_SCOPE_BOTH_E;
+    return distances(env, h, run_kcore, &a);
+}
+
 /* tgo_result_rows: Object[5] = {long[] rowKeys, long[] rowEntryBegin, long[] rowByteBegin,
  * long[] entryLimitValuePos, byte[] entryBytes}, or NULL on error (status: lastError; a result
  * beyond the int32 index range of a Java array: IllegalStateException). */

@@ -44,8 +44,9 @@ import java.util.concurrent.Future;
  * Supported: tmain's PageRankVertexProgram, ShortestDistanceVertexProgram and
  * OLAPTest.DegreeCounter (matched by class name; their parameters are read from
  * storeState(), or the DegreeCounter's length field), and a ConnectedComponentVertexProgram
- * (weakly connected components over bothE, tgo_components) and a TriangleCountVertexProgram
- * (triangles and clustering coefficients of the simple undirected projection, tgo_triangles).
+ * (weakly connected components over bothE, tgo_components), a TriangleCountVertexProgram
+ * (triangles and clustering coefficients of the simple undirected projection, tgo_triangles) and
+ * a KCoreVertexProgram (core numbers of the same projection, tgo_kcore).
  *
  * Write-back (FulgoraGraphComputer.java:248-305): with Persist.VERTEX_PROPERTIES the compute
  * keys are encoded on the device (tgo_result_rows: single-cardinality property entries, one
@@ -540,6 +541,8 @@ public class GpuGraphComputer implements TitanGraphComputer {
                     return new ConnectedComponent();
                 case "com.thinkaurelius.titan.olap.TriangleCountVertexProgram":
                     return new TriangleCount();
+                case "com.thinkaurelius.titan.olap.KCoreVertexProgram":
+                    return new KCore();
                 default:
                     throw new TitanException("vertex program " + p.getClass().getName() + " is not supported on the GPU path");
             }
@@ -708,6 +711,32 @@ public class GpuGraphComputer implements TitanGraphComputer {
         void emit(long[] ids, Map<String, Object> values, FulgoraMapEmitter emitter) {
             long[] t = (long[]) values.get(TRIANGLES);
             for (int i = 0; i < ids.length; i++) emitter.emit(ids[i], t[i]);
+        }
+    }
+
+    /**
+     * k-core decomposition over bothE on the simple undirected projection (tgo_kcore): CORE = the
+     * largest k such that the vertex lies in a subgraph whose vertices all have at least k
+     * neighbours.  The iteration reported is the number of distinct core values (the peel's
+     * levels), known after run().
+     */
+    static final class KCore extends DeviceProgram {
+        static final String CORE = "titan.kCore.coreNumber";
+        private int levels;
+        int scope() { return TgoNative.SCOPE_BOTH_E; }
+        int iterations() { return levels; }
+        int resultKind() { return TgoNative.RESULT_CORE; }
+        String[] computeKeys() { return new String[]{CORE}; }
+        int[] computeKeyTypes() { return new int[]{TgoNative.DT_LONG}; }
+        Map<String, Object> run(long ctx) {
+            Map<String, Object> v = new HashMap<>();
+            v.put(CORE, TgoNative.checked(ctx, TgoNative.kcore(ctx)));
+            levels = (int) TgoNative.stats(ctx)[3];
+            return v;
+        }
+        void emit(long[] ids, Map<String, Object> values, FulgoraMapEmitter emitter) {
+            long[] c = (long[]) values.get(CORE);
+            for (int i = 0; i < ids.length; i++) emitter.emit(ids[i], c[i]);
         }
     }
 }

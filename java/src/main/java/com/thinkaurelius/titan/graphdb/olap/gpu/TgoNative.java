@@ -89,12 +89,18 @@ public final class TgoNative {
      */
     public static native long[] triangles(long ctx);
 
+    /**
+     * tgo_kcore over a bothE load: every vertex's core number on the simple undirected projection,
+     * in row order; null on failure.  stats()[3] then holds the levels: the distinct core values.
+     */
+    public static native long[] kcore(long ctx);
+
     /** tgo_stats_get: {ghostVertices, truncatedResults, skippedRows, iterations, loadMs, lastKernelMs}. */
     public static native double[] stats(long ctx);
 
     /** tgo_result_kind */
     public static final int RESULT_DISTANCE = 0, RESULT_PAGERANK = 1, RESULT_DEGREE = 2, RESULT_COMPONENT = 4,
-            RESULT_TRIANGLES = 5;
+            RESULT_TRIANGLES = 5, RESULT_CORE = 6;
     /**
      * tgo_result_rows: the edgestore entries (single-cardinality property entries) of the last
      * program's compute keys, as {long[] rowKeys, long[] rowEntryBegin, long[] rowByteBegin,

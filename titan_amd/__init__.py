@@ -6,8 +6,9 @@ TitanGraphComputer API plus a thin ctypes binding; it has no CPU fallback.
 """
 from .engine import Engine, Rows, Schema, TitanException, rmat_edges, pick_roots, synth_rows  # noqa: F401
 from .computer import (  # noqa: F401
-    ClusterCountMapReduce, ClusterPopulationMapReduce, ConnectedComponentVertexProgram,
-    DegreeCounter, DegreeMapper, ExecutionException, GpuGraph, GpuGraphComputer, KeyValue,
+    ClusterCountMapReduce, ClusterPopulationMapReduce, ConnectedComponentVertexProgram, CoreSizeMapReduce,
+    DegeneracyMapReduce, DegreeCounter, DegreeMapper, ExecutionException, GpuGraph, GpuGraphComputer,
+    KCoreVertexProgram, KeyValue,
     PageRankMapReduce, PageRankVertexProgram, ShortestDistanceMapReduce,
     ShortestDistanceVertexProgram, TitanGraphComputer, TransitivityMapReduce, TriangleCountMapReduce,
     TriangleCountVertexProgram,
@@ -26,4 +27,5 @@ __all__ = [
     "Messenger", "Vertices", "EdgeExpr", "TraversalVertexProgram",
     "ConnectedComponentVertexProgram", "ClusterPopulationMapReduce", "ClusterCountMapReduce",
     "TriangleCountVertexProgram", "TriangleCountMapReduce", "TransitivityMapReduce",
+    "KCoreVertexProgram", "DegeneracyMapReduce", "CoreSizeMapReduce",
 ]

@@ -33,6 +33,7 @@ ORDER_ASC, ORDER_DESC = 0, 1
 RESULT_DISTANCE, RESULT_PAGERANK, RESULT_DEGREE, RESULT_VALUES = 0, 1, 2, 3
 RESULT_COMPONENT = 4
 RESULT_TRIANGLES = 5
+RESULT_CORE = 6
 CC_HOOK, CC_PROPAGATE = 0, 1     # tgo_cc_path
 SSSP_HOP_BOUNDED, SSSP_DELTA = 0, 1
 FLAG_STATS = 1
@@ -41,6 +42,8 @@ TUNE_DS_SMALL = 8
 TUNE_MS_STAY, TUNE_MS_SPARSE = 9, 10
 TUNE_MS_HEAD = 13   # tgo_bfs_multi: entries of its own lists a long-list lane probes before the whole wave
 TUNE_TRI_WAVE_ROW, TUNE_TRI_BLOCK_ROW = 11, 12   # tgo_triangles: forward-row lengths of the wave / workgroup paths
+# tgo_kcore: neighbourhood size of the wave path, alive vertices one workgroup finishes, a workgroup's queue
+TUNE_CORE_WAVE_ROW, TUNE_CORE_TAIL, TUNE_CORE_LDS_QUEUE = 14, 15, 16
 TRACE_JSON, TRACE_ROCTX = 1, 2   # tgo_trace_enable flags
 DIST_ABSENT = -(1 << 63)
 ABI_VERSION = 2
@@ -149,6 +152,15 @@ class TriInfo(C.Structure):
                 ("max_forward", C.c_int64)]
 
 
+class CoreArgs(C.Structure):
+    _fields_ = [("scope", C.c_int32), ("flags", C.c_int32)]
+
+
+class CoreInfo(C.Structure):
+    _fields_ = [("degeneracy", C.c_int64), ("innermost", C.c_int64), ("simple_edges", C.c_int64),
+                ("levels", C.c_int32), ("rounds", C.c_int32)]
+
+
 class GatherArgs(C.Structure):
     _fields_ = [("scope", C.c_int32), ("value_type", C.c_int32), ("combiner", C.c_int32), ("edge_fn", C.c_int32)]
 
@@ -178,6 +190,7 @@ EXPORTS = [
     "tgo_gather", "tgo_combine_global", "tgo_dense_ids", "tgo_decode_edge_entry", "tgo_result_rows",
     "tgo_gather_lists", "tgo_result_rows_values", "tgo_set_edge_program",
     "tgo_components", "tgo_copy_components", "tgo_triangles", "tgo_copy_triangles",
+    "tgo_kcore", "tgo_copy_cores",
     "tgo_rmat_edges", "tgo_rmat_edges_device", "tgo_rmat_partition_device", "tgo_pick_roots", "tgo_synth_rows",
     # titan_gpu_olap_part.h (1-D vertex-partitioned multi-GPU)
     "tgo_load_partition", "tgo_part_layout", "tgo_load_partition_layout", "tgo_part_bfs_begin", "tgo_part_bfs_td", "tgo_part_bfs_claim", "tgo_part_bfs_bu",
@@ -238,6 +251,8 @@ def load() -> C.CDLL:
         "tgo_copy_components": (C.c_int, [vp, _i64p]),
         "tgo_triangles": (C.c_int, [vp, P(TriArgs), _i64p, P(TriInfo)]),
         "tgo_copy_triangles": (C.c_int, [vp, _i64p, _i64p, C.POINTER(C.c_double)]),
+        "tgo_kcore": (C.c_int, [vp, P(CoreArgs), _i64p, P(CoreInfo)]),
+        "tgo_copy_cores": (C.c_int, [vp, _i64p]),
         "tgo_pagerank": (C.c_int, [vp, P(PrArgs), C.POINTER(C.c_double)]),
         "tgo_walkcount": (C.c_int, [vp, C.c_int32, _i32p]),
         "tgo_stats_get": (C.c_int, [vp, P(Stats)]),

@@ -401,6 +401,26 @@ class TriangleCountVertexProgram(VertexProgram):
         return TriangleCountVertexProgram.Builder()
 
 
+class KCoreVertexProgram(VertexProgram):
+    """k-core decomposition over bothE on the simple undirected projection (tgo_kcore): parallel
+    edges, the two directions of a pair and self-loops collapse.  CORE = the vertex's core number
+    (Long): the largest k such that it lies in a subgraph whose vertices all have at least k
+    neighbours; 0 without a neighbour.  memory.getIteration() is the number of distinct core values
+    (the peel's levels), not the supersteps an H-index iteration would take.  Result graph and
+    persist preference as ShortestDistanceVertexProgram."""
+    CORE = "titan.kCore.coreNumber"
+    compute_keys = (CORE,)
+    scope_name = "bothE"
+
+    class Builder:
+        def create(self, graph=None):
+            return KCoreVertexProgram()
+
+    @staticmethod
+    def build():
+        return KCoreVertexProgram.Builder()
+
+
 # ----------------------------------------------------------------------------- map-reduces
 class MapReduce:
     memory_key = ""
@@ -549,6 +569,41 @@ class TransitivityMapReduce(MapReduce):
         return 3 * t / w if w else 0.0
 
 
+class DegeneracyMapReduce(MapReduce):
+    """The graph's degeneracy: the largest core number (0 without the property)."""
+    DEFAULT_MEMORY_KEY = "degeneracy"
+
+    def __init__(self, key=DEFAULT_MEMORY_KEY):
+        self.memory_key = key
+
+    @staticmethod
+    def build():
+        return _MemoryKeyBuilder(DegeneracyMapReduce)
+
+    def emit(self, ids, props):
+        core = props.get(KCoreVertexProgram.CORE)
+        return 0 if core is None or len(core) == 0 else int(np.max(np.asarray(core, dtype=np.int64)))
+
+
+class CoreSizeMapReduce(MapReduce):
+    """Core number -> number of vertices carrying it."""
+    DEFAULT_MEMORY_KEY = "coreSizes"
+
+    def __init__(self, key=DEFAULT_MEMORY_KEY):
+        self.memory_key = key
+
+    @staticmethod
+    def build():
+        return _MemoryKeyBuilder(CoreSizeMapReduce)
+
+    def emit(self, ids, props):
+        core = props.get(KCoreVertexProgram.CORE)
+        if core is None:
+            return {}
+        u, c = np.unique(np.asarray(core, dtype=np.int64), return_counts=True)
+        return {int(k): int(v) for k, v in zip(u, c)}
+
+
 class DegreeMapper(MapReduce):
     DEGREE_RESULT = "degrees"                 # OLAPTest.java:420
     memory_key = DEGREE_RESULT
@@ -673,7 +728,8 @@ class GpuGraphComputer(TitanGraphComputer):
                     DegreeCounter: (L.RESULT_DEGREE, (DegreeCounter.DEGREE,)),
                     ConnectedComponentVertexProgram: (L.RESULT_COMPONENT, (ConnectedComponentVertexProgram.COMPONENT,)),
                     TriangleCountVertexProgram: (L.RESULT_TRIANGLES, (TriangleCountVertexProgram.TRIANGLES,
-                                                                      TriangleCountVertexProgram.CLUSTERING))}
+                                                                      TriangleCountVertexProgram.CLUSTERING)),
+                    KCoreVertexProgram: (L.RESULT_CORE, (KCoreVertexProgram.CORE,))}
 
     def _result_mode(self):
         """resultMode if set, else the program's preferred (ResultGraph, Persist) as Fulgora
@@ -775,6 +831,11 @@ class GpuGraphComputer(TitanGraphComputer):
             props[TriangleCountVertexProgram.CLUSTERING] = lcc
             props[TriangleCountVertexProgram.DEGREE] = deg        # for TransitivityMapReduce; not a compute key
             iteration = 1
+            ids = eng.vertex_ids()
+        elif isinstance(p, KCoreVertexProgram):
+            eng = self.graph.engine_for(L.SCOPE_BOTH_E)
+            props[KCoreVertexProgram.CORE], info = eng.kcore()
+            iteration = info["levels"]
             ids = eng.vertex_ids()
         else:
             raise TitanException(L.TGO_E_UNSUPPORTED, f"vertex program {type(p).__name__} is not supported on the GPU path")

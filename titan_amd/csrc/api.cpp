@@ -673,6 +673,22 @@ int tgo_set_tuning(tgo_ctx* ctx, int32_t key, double value) {
         (key == TGO_TUNE_TRI_WAVE_ROW ? ctx->tri_wave_row : ctx->tri_block_row) = value < 0.0 ? -1 : static_cast<int64_t>(value);
         return TGO_OK;
     }
+    case TGO_TUNE_CORE_WAVE_ROW:
+        if (!(value < 0.0) && !(value >= 1.0 && value <= 9.0e15 && value == static_cast<double>(static_cast<int64_t>(value))))
+            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_CORE_WAVE_ROW: a neighbourhood size >= 1 (< 0: the default)");
+        ctx->core_wave_row = value < 0.0 ? -1 : static_cast<int64_t>(value);
+        return TGO_OK;
+    case TGO_TUNE_CORE_TAIL:
+        if (!(value < 0.0) && !(value <= 9.0e15 && value == static_cast<double>(static_cast<int64_t>(value))))
+            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_CORE_TAIL: a whole number of vertices >= 0 (0 = never; < 0: the default)");
+        ctx->core_tail = value < 0.0 ? -1 : static_cast<int64_t>(value);
+        return TGO_OK;
+    case TGO_TUNE_CORE_LDS_QUEUE:
+        if (!(value < 0.0) && !(value >= 1.0 && value <= static_cast<double>(kCoreQueue) &&
+                                value == static_cast<double>(static_cast<int64_t>(value))))
+            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_CORE_LDS_QUEUE: entries in [1, 4096] (< 0: the default)");
+        ctx->core_lds_queue = value < 0.0 ? -1 : static_cast<int64_t>(value);
+        return TGO_OK;
     default:
         return fail(ctx, TGO_E_INVALID, "tgo_set_tuning: unknown key");
     }
@@ -1133,6 +1149,221 @@ int tgo_copy_triangles(tgo_ctx* ctx, int64_t* tri_out, int64_t* deg_out, double*
     return TGO_OK;
 }
 
+// ------------------------------------------------------------------ k-core decomposition
+// k-core (core.hip).  The backward lists and the totals' words live with the graph (dev_alloc:
+// released with it), beside the forward lists and degrees they share with tgo_triangles.  Per run:
+// working degrees (int32, the core numbers at the end) = sc.level, cores in internal order =
+// sc.dist, the alive lists = sc.q[0] / sc.q[1], the level queues = sc.vec[0] / sc.vec[1] (as
+// int32), row-order staging = sc.msg.  Level control: Counters through publish_turn / wait_publish.
+// Defaults of TGO_TUNE_CORE_WAVE_ROW / _TAIL / _LDS_QUEUE: DESIGN.md 4.6 has the sweep they come from.
+constexpr int64_t kCoreWaveRow = 64, kCoreTail = 1024, kCoreLdsQueue = 256;
+
+static int core_backward_lists(tgo_ctx* ctx) {
+    DevGraph& g = ctx->g;
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    const int64_t n = g.n;
+    DevSpan span(st, "kcore.lists", {"forward_entries", g.tri_fnnz});
+    // the three arrays reach the graph only when all of them are built: a failure on the way
+    // releases what it allocated, and the next call starts over
+    unsigned long long* tot = nullptr;
+    int64_t* boff = nullptr;
+    int32_t* badj = nullptr;
+    struct Undo {
+        tgo_ctx* ctx; unsigned long long*& tot; int64_t*& boff; int32_t*& badj; int64_t n, fnnz;
+        bool keep = false;
+        ~Undo() {
+            if (keep) return;
+            dev_free(ctx, badj, fnnz);
+            dev_free(ctx, boff, n + 1);
+            dev_free(ctx, tot, 2);
+        }
+    } undo{ctx, tot, boff, badj, n, g.tri_fnnz};
+    HIP_TRY(dev_alloc(ctx, tot, 2));
+    HIP_TRY(dev_alloc(ctx, boff, n + 1));
+    HIP_TRY(dev_alloc(ctx, badj, g.tri_fnnz));
+    // count, scan, fill: |bwd(v)| in sc.qdeg (n + 2), the fill's cursors in sc.qpre (n + 2)
+    HIP_TRY(hipMemsetAsync(s.qdeg, 0, (n + 1) * sizeof(int64_t), st));
+    HIP_TRY(k_core_bwd_count(g.tri_fadj, g.tri_fnnz, s.qdeg, st));
+    HIP_TRY(scan_exclusive_i64(s.cub_tmp, s.cub_bytes, s.qdeg, boff, n + 1, st));
+    HIP_TRY(hipMemcpyAsync(s.qpre, boff, (n + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    int64_t bnnz = -1;
+    HIP_TRY(hipMemcpyAsync(&bnnz, boff + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // (checked before the fill: its cursors stay inside badj only when the counts add up)
+    if (bnnz != g.tri_fnnz) return fail(ctx, TGO_E_HIP, "backward lists: inconsistent entry count");
+    HIP_TRY(k_core_bwd_fill(g.tri_foff, g.tri_fadj, n, s.qpre, badj, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    undo.keep = true;
+    g.core_tot = tot;
+    g.core_boff = boff;
+    g.core_badj = badj;
+    ctx->st.device_bytes = ctx->dev_bytes;
+    return TGO_OK;
+}
+
+// One publish of the level counters, which are zero again afterwards.
+static int core_turn(tgo_ctx* ctx) {
+    Scratch& s = ctx->sc;
+    const unsigned long long seq = ++s.pub_seq;
+    HIP_TRY(k_publish_turn(s.cnt, s.hcnt_dev, seq, nullptr, ctx->stream));
+    int rc = wait_publish(ctx, seq);
+    if (rc) return rc;
+    if (s.hcnt->err) return fail(ctx, TGO_E_HIP, "k-core peel: a queue overflowed (inconsistent lists)");
+    return TGO_OK;
+}
+
+// The peel: deg (a copy of d(v)) ends as the core numbers.  Out: levels, peel launches, the largest
+// core number and the vertices peeled at it.
+static int core_peel_levels(tgo_ctx* ctx, int32_t* deg, int32_t& levels, int32_t& rounds, int64_t& top,
+                            int64_t& innermost) {
+    DevGraph& g = ctx->g;
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    const int64_t n = g.n;
+    const CoreView lists{g.tri_foff, g.tri_fadj, g.core_boff, g.core_badj};
+    const int64_t wave_row = tuned(ctx->core_wave_row, kCoreWaveRow);
+    const int64_t tail = std::min<int64_t>(tuned(ctx->core_tail, kCoreTail), kCoreQueue);
+    const int64_t lds_cap = tuned(ctx->core_lds_queue, kCoreLdsQueue);
+    int32_t* const alive_list[2] = {s.q[0], s.q[1]};
+    int32_t* const queue[2] = {reinterpret_cast<int32_t*>(s.vec[0]), reinterpret_cast<int32_t*>(s.vec[1])};
+    auto min_of = [](unsigned long long word) {        // Counters::red[0] of core_scan / core_peel
+        return word ? static_cast<int64_t>(INT32_MAX) - static_cast<int64_t>(word) : INT64_MAX;
+    };
+    int rc = TGO_OK;
+    HIP_TRY(k_core_deg_init(g.tri_deg, n, deg, st));
+    HIP_TRY(k_level_prep(s.cnt, nullptr, 0, nullptr, st));
+    // the smallest degree: a scan that queues nothing
+    HIP_TRY(k_core_scan(nullptr, n, deg, -1, nullptr, nullptr, s.cnt, st));
+    if ((rc = core_turn(ctx))) return rc;
+    int64_t next_k = min_of(s.hcnt->red[0]);
+    int64_t alive = n, len = n, k = -1;
+    const int32_t* list = nullptr;      // the alive list in use (null: every vertex)
+    int spare = 0;                      // the alive_list buffer it is not in
+    while (alive > 0) {
+        if (next_k == INT64_MAX) return fail(ctx, TGO_E_HIP, "k-core peel: alive vertices without a degree");
+        if (tail > 0 && alive <= tail) {
+            if (len > 2 * alive) {      // the one workgroup scans the list once per level: compact it first
+                HIP_TRY(k_core_scan(list, len, deg, static_cast<int32_t>(k), nullptr, alive_list[spare], s.cnt, st));
+                if ((rc = core_turn(ctx))) return rc;
+                list = alive_list[spare];
+                spare ^= 1;
+                len = static_cast<int64_t>(s.hcnt->mf);
+                if (len != alive) return fail(ctx, TGO_E_HIP, "k-core peel: inconsistent alive count");
+            }
+            HIP_TRY(k_core_tail(list, len, lists, deg, static_cast<int32_t>(k), wave_row, s.cnt, st));
+            if ((rc = core_turn(ctx))) return rc;
+            ++rounds;
+            levels += static_cast<int32_t>(s.hcnt->qlen);
+            innermost = static_cast<int64_t>(s.hcnt->mf);
+            top = static_cast<int64_t>(s.hcnt->red[0]);
+            return TGO_OK;
+        }
+        k = next_k;
+        const bool rebuild = 2 * alive <= len;      // the list has at least halved
+        HIP_TRY(k_core_scan(list, len, deg, static_cast<int32_t>(k), queue[0], rebuild ? alive_list[spare] : nullptr,
+                            s.cnt, st));
+        if ((rc = core_turn(ctx))) return rc;
+        int64_t qlen = static_cast<int64_t>(s.hcnt->qlen);
+        next_k = min_of(s.hcnt->red[0]);
+        if (rebuild) {
+            list = alive_list[spare];
+            spare ^= 1;
+            len = static_cast<int64_t>(s.hcnt->mf);
+        }
+        // the minimum named a vertex that the level before went on to drop and peel: nobody is
+        // left at k, and this scan's minimum is exact (nothing has changed since it ran)
+        if (qlen == 0) continue;
+        if (qlen > alive) return fail(ctx, TGO_E_HIP, "k-core peel: inconsistent level queue");
+        ++levels;
+        top = k;
+        innermost = qlen;
+        alive -= qlen;
+        for (int cur = 0; qlen > 0 && k > 0; cur ^= 1) {    // (a vertex of level 0 has no neighbour)
+            HIP_TRY(k_core_peel(queue[cur], qlen, lists, deg, static_cast<int32_t>(k), wave_row, lds_cap, queue[cur ^ 1],
+                                n, s.cnt, st));
+            if ((rc = core_turn(ctx))) return rc;
+            ++rounds;
+            const int64_t drops = static_cast<int64_t>(s.hcnt->mf);     // queued for the next launch or not
+            qlen = static_cast<int64_t>(s.hcnt->qlen);
+            if (drops > alive || qlen > drops) return fail(ctx, TGO_E_HIP, "k-core peel: inconsistent drop count");
+            innermost += drops;
+            alive -= drops;
+            next_k = std::min(next_k, min_of(s.hcnt->red[0]));
+        }
+    }
+    return TGO_OK;
+}
+
+int tgo_kcore(tgo_ctx* ctx, const tgo_core_args* a, int64_t* core_out, tgo_core_info* info) {
+    if (!ctx) return TGO_E_INVALID;
+    ctx->res_kind = -1;
+    if (!a) return fail(ctx, TGO_E_INVALID, "null args");
+    int rc = check_program(ctx, a->scope);
+    if (rc) return rc;
+    if (a->scope != TGO_SCOPE_BOTH_E)
+        return fail(ctx, TGO_E_INVALID, "core numbers are computed over bothE; load the graph with TGO_SCOPE_BOTH_E");
+    if (a->flags != 0) return fail(ctx, TGO_E_INVALID, "tgo_core_args.flags must be 0");
+    if (ctx->g.partitioned) return fail(ctx, TGO_E_UNSUPPORTED, "core numbers are computed on a one-GPU load");
+    if (ctx->g.has_transpose)
+        return fail(ctx, TGO_E_UNSUPPORTED,
+                    "the loaded OUT and IN lists are not each other's transpose (tgo_load_csr with asymmetric rows): "
+                    "the neighbour relation is asymmetric, core numbers are not defined on it");
+    (void)hipSetDevice(ctx->opts.device);
+    DevGraph& g = ctx->g;
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    const int64_t n = g.n;
+    if (!g.tri_fadj && (rc = tri_forward_lists(ctx))) return rc;
+    if (!g.core_badj && (rc = core_backward_lists(ctx))) return rc;
+    int32_t* const deg = s.level;
+    int64_t* const core = s.dist;
+    HIP_TRY(hipEventRecord(ctx->ev0, st));
+    int32_t levels = 0, rounds = 0;
+    int64_t top = 0, innermost = 0;
+    unsigned long long tot[2] = {0, 0};
+    if (g.tri_fnnz == 0) {
+        // no simple edge: nothing is peeled, every core number is 0 and the info stays zero
+        HIP_TRY(k_fill_i64(core, 0, n, st));
+    } else {
+        {
+            DevSpan span(st, "kcore.peel", {"simple_edges", g.tri_fnnz});
+            if ((rc = core_peel_levels(ctx, deg, levels, rounds, top, innermost))) return rc;
+        }
+        DevSpan span(st, "kcore.finish");
+        HIP_TRY(hipMemsetAsync(g.core_tot, 0, 2 * sizeof(unsigned long long), st));
+        HIP_TRY(k_core_finish(deg, n, static_cast<int32_t>(top), core, g.core_tot, st));
+        span.end();
+        HIP_TRY(hipMemcpyAsync(tot, g.core_tot, sizeof tot, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipEventRecord(ctx->ev1, st));
+    HIP_TRY(hipEventSynchronize(ctx->ev1));
+    trace_resolve(st);
+    // the device's own count of the result against the level loop's bookkeeping
+    if (static_cast<int64_t>(tot[1]) != top || static_cast<int64_t>(tot[0]) != innermost)
+        return fail(ctx, TGO_E_HIP, "k-core: the core numbers disagree with the peel's level counts");
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    ctx->st.last_kernel_ms = ms;
+    ctx->st.iterations = levels;
+    if (info) *info = tgo_core_info{top, innermost, g.tri_fnnz, levels, rounds};
+    if (core_out && (rc = tri_copy_out(ctx, core, core_out))) return rc;
+    ctx->res_kind = TGO_RESULT_CORE;
+    ctx->res_empty = false;
+    ctx->res_src = ResultSource{core, nullptr};
+    return TGO_OK;
+}
+
+int tgo_copy_cores(tgo_ctx* ctx, int64_t* core_out) {
+    if (!ctx || !core_out) return TGO_E_INVALID;
+    if (!ctx->loaded) return fail(ctx, TGO_E_STATE, "no graph loaded");
+    if (ctx->res_kind != TGO_RESULT_CORE)
+        return fail(ctx, TGO_E_STATE, "tgo_kcore is not the last program run on this ctx");
+    (void)hipSetDevice(ctx->opts.device);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return tri_copy_out(ctx, ctx->sc.dist, core_out);
+}
+
 int tgo_pagerank(tgo_ctx* ctx, const tgo_pr_args* a, double* pr_out) {
     if (!ctx) return TGO_E_INVALID;
     ctx->res_kind = -1;
@@ -1309,7 +1540,7 @@ static int result_rows_impl(tgo_ctx* ctx, const tgo_result_args* a, const Result
 int tgo_result_rows(tgo_ctx* ctx, const tgo_result_args* a, tgo_result_size* size, const tgo_rows_buf* out) {
     if (!ctx) return TGO_E_INVALID;
     if (!a || !size) return fail(ctx, TGO_E_INVALID, "null args");
-    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_TRIANGLES || a->kind == TGO_RESULT_VALUES)
+    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_CORE || a->kind == TGO_RESULT_VALUES)
         return fail(ctx, TGO_E_INVALID, "invalid result kind");
     if (ctx->res_kind != a->kind)
         return fail(ctx, TGO_E_STATE, "no finished program of that kind is the last one run on this ctx");
@@ -1320,6 +1551,10 @@ int tgo_result_rows(tgo_ctx* ctx, const tgo_result_args* a, tgo_result_size* siz
                 return fail(ctx, TGO_E_INVALID, "a value of an Integer compute key is out of int range");
     if (a->kind == TGO_RESULT_TRIANGLES && a->datatypes[0] == TGO_DT_INTEGER && ctx->tri_max > INT32_MAX)
         return fail(ctx, TGO_E_INVALID, "a value of an Integer compute key is out of int range");
+    // a core number is at most d(v) < 2^31: an Integer key holds every one
+    if (a->kind == TGO_RESULT_CORE && a->datatypes[0] != TGO_DT_LONG && a->datatypes[0] != TGO_DT_INTEGER &&
+        a->datatypes[0] != TGO_DT_OBJECT)
+        return fail(ctx, TGO_E_INVALID, "the core number's compute key must be Long, Integer or generic (Object)");
     return result_rows_impl(ctx, a, ctx->res_src, ctx->res_empty, size, out);
 }
 

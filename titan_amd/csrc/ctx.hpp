@@ -84,6 +84,10 @@ struct tgo_ctx {
     int64_t tri_wave_row = -1;  // tgo_set_tuning(TGO_TUNE_TRI_WAVE_ROW / _BLOCK_ROW): forward-row lengths from
     int64_t tri_block_row = -1; // which a wave / a workgroup takes the row; < 0: the defaults (kTriWaveRow / kTriBlockRow)
     int64_t tri_max = 0;        // largest count of the last tgo_triangles (an Integer key's range check)
+    int64_t core_wave_row = -1; // tgo_set_tuning(TGO_TUNE_CORE_WAVE_ROW): neighbourhood size from which a wave walks it
+    int64_t core_tail = -1;     // tgo_set_tuning(TGO_TUNE_CORE_TAIL): alive vertices one workgroup finishes; 0 = never
+    int64_t core_lds_queue = -1;    // tgo_set_tuning(TGO_TUNE_CORE_LDS_QUEUE): entries of a workgroup's own queue
+                                // (< 0: the defaults kCoreWaveRow / kCoreTail / kCoreLdsQueue)
     // state a native partitioned driver keeps between runs on this graph (part_driver.cpp:
     // the PageRank ghost lists); dropped with the graph
     std::shared_ptr<void> part_state;

@@ -476,6 +476,11 @@ struct DevGraph {
     unsigned long long* tri_tot = nullptr;   // 16 words: [0] longest forward row; per run: [1] sum tri,
                                     // [2] wedges, [3] sum d, [4] max tri, [5..8] the row queues' counts and tickets
     int64_t tri_fnnz = 0, tri_max_fwd = 0;
+    // backward lists (tgo_kcore, built on its first run): bwd(v) = the distinct neighbours u > v, the
+    // transpose of the forward lists (tri_fnnz entries, unordered inside a row)
+    int64_t* core_boff = nullptr;   // n + 1
+    int32_t* core_badj = nullptr;   // tri_fnnz
+    unsigned long long* core_tot = nullptr;  // 2 words per run: vertices of the innermost core, max core
 };
 
 // Views of the loaded scope.
@@ -923,6 +928,35 @@ hipError_t k_tri_count(const int64_t* foff, const int32_t* fadj, int64_t n, int6
                        hipStream_t s);
 hipError_t k_tri_finish(const int64_t* tri, const int64_t* deg, int64_t n, double* lcc, unsigned long long* tot,
                         hipStream_t s);
+
+// k-core decomposition (core.hip).  Backward lists: k_core_bwd_count adds |bwd(u)| to bcnt (zero
+// before), k_core_bwd_fill writes the rows through cursor (a copy of their scanned offsets).
+// deg (int32, k_core_deg_init: a copy of d(v)) is peeled in place and ends as the core numbers.
+// k_core_scan (level k over the alive list; list null = every vertex; queue null = none): cnt->qlen vertices with
+// deg == k to queue, with keep the cnt->mf vertices with deg > k to keep, cnt->red[0] =
+// INT32_MAX - the smallest deg > k (0: none).  k_core_peel (one launch of level k): the drops its
+// workgroups do not peel themselves to next (cnt->qlen), cnt->mf += every drop, cnt->red[0] as
+// above over the degrees it lowered, cnt->err on a full queue.  k_core_tail (one workgroup, every level above k_prev; at most
+// kCoreQueue alive vertices): cnt->qlen = levels, cnt->mf = vertices of the last level,
+// cnt->red[0] = its k, cnt->red[1] = steps.  k_core_finish: core = deg as int64, tot[0] += vertices
+// with core == top, tot[1] = max core.
+constexpr int kCoreQueue = 4096;    // entries of a workgroup's LDS queue buffer (two buffers: 32 KB)
+struct CoreView {
+    const int64_t* foff; const int32_t* fadj;
+    const int64_t* boff; const int32_t* badj;
+};
+hipError_t k_core_bwd_count(const int32_t* fadj, int64_t fnnz, int64_t* bcnt, hipStream_t s);
+hipError_t k_core_bwd_fill(const int64_t* foff, const int32_t* fadj, int64_t n, int64_t* cursor, int32_t* badj,
+                           hipStream_t s);
+hipError_t k_core_deg_init(const int64_t* d, int64_t n, int32_t* deg, hipStream_t s);
+hipError_t k_core_scan(const int32_t* list, int64_t len, const int32_t* deg, int32_t k, int32_t* queue, int32_t* keep,
+                       Counters* cnt, hipStream_t s);
+hipError_t k_core_peel(const int32_t* cur, int64_t qlen, const CoreView& g, int32_t* deg, int32_t k, int64_t wave_row,
+                       int64_t lds_cap, int32_t* next, int64_t n, Counters* cnt, hipStream_t s);
+hipError_t k_core_tail(const int32_t* list, int64_t len, const CoreView& g, int32_t* deg, int32_t k_prev, int64_t wave_row,
+                       Counters* cnt, hipStream_t s);
+hipError_t k_core_finish(const int32_t* deg, int64_t n, int32_t top, int64_t* core, unsigned long long* tot,
+                         hipStream_t s);
 
 // PageRank gather diagnostics: [diag_lo, diag_hi) = only sources in this range are gathered
 // (the others read as 0; results invalid) — attributes the update's time to source ranges.

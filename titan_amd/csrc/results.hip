@@ -73,7 +73,7 @@ __device__ inline bool value_of(const ResArgs& a, const void* v0, const void* v1
         bits = static_cast<const uint64_t*>(k == 0 ? v0 : v1)[v];
         return true;
     }
-    if (a.kind == TGO_RESULT_COMPONENT) {       // a label on every executed vertex
+    if (a.kind == TGO_RESULT_COMPONENT || a.kind == TGO_RESULT_CORE) {   // a label / core number on every executed vertex
         bits = static_cast<const uint64_t*>(v0)[v];
         return true;
     }
@@ -185,15 +185,16 @@ int encode_results(const ResultSource& src, const tgo_result_args* a, const int3
     ra.kind = a->kind;
     ra.nkeys = a->kind == TGO_RESULT_PAGERANK || a->kind == TGO_RESULT_TRIANGLES ? 2 : 1;
     ra.rel_base = a->relation_id_base;
-    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_TRIANGLES) { err = "unknown result kind"; return TGO_E_INVALID; }
-    int want[6][2] = {{TGO_DT_LONG, 0}, {TGO_DT_DOUBLE, TGO_DT_DOUBLE}, {TGO_DT_INTEGER, 0}, {0, 0}, {TGO_DT_LONG, 0},
-                      {TGO_DT_LONG, TGO_DT_DOUBLE}};
+    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_CORE) { err = "unknown result kind"; return TGO_E_INVALID; }
+    int want[7][2] = {{TGO_DT_LONG, 0}, {TGO_DT_DOUBLE, TGO_DT_DOUBLE}, {TGO_DT_INTEGER, 0}, {0, 0}, {TGO_DT_LONG, 0},
+                      {TGO_DT_LONG, TGO_DT_DOUBLE}, {TGO_DT_LONG, 0}};
     // StandardSerializer registration numbers of the value classes (:71-81): Long 13, Double 20, Integer 12
     // (per key where a kind's two keys differ: the triangle count is a Long, its coefficient a Double)
-    uint8_t reg[6][2] = {{0x80 | 13, 0}, {0x80 | 20, 0x80 | 20}, {0x80 | 12, 0}, {0, 0}, {0x80 | 13, 0},
-                         {0x80 | 13, 0x80 | 20}};
-    if (a->kind == TGO_RESULT_COMPONENT || a->kind == TGO_RESULT_TRIANGLES) {
-        // the labels / counts are longs: a Long key, an Integer key (the caller checked the range)
+    uint8_t reg[7][2] = {{0x80 | 13, 0}, {0x80 | 20, 0x80 | 20}, {0x80 | 12, 0}, {0, 0}, {0x80 | 13, 0},
+                         {0x80 | 13, 0x80 | 20}, {0x80 | 13, 0}};
+    const bool long_or_int = a->kind == TGO_RESULT_COMPONENT || a->kind == TGO_RESULT_TRIANGLES || a->kind == TGO_RESULT_CORE;
+    if (long_or_int) {
+        // the labels / counts / core numbers are longs: a Long key, an Integer key (the caller checked the range)
         // or a generic key holding Longs — the int64 encoder of a generic program's values
         ra.vdt = a->datatypes[0] == TGO_DT_INTEGER ? TGO_DT_INTEGER : TGO_DT_LONG;
         want[a->kind][0] = ra.vdt;
@@ -215,7 +216,7 @@ int encode_results(const ResultSource& src, const tgo_result_args* a, const int3
             return TGO_E_INVALID;
         }
     }
-    const bool multi_dt = a->kind == TGO_RESULT_VALUES || a->kind == TGO_RESULT_COMPONENT || a->kind == TGO_RESULT_TRIANGLES;
+    const bool multi_dt = a->kind == TGO_RESULT_VALUES || long_or_int;
     // by key here, by column position below; the second key of a kind is always a Double
     const int key_varint[2] = {a->kind == TGO_RESULT_DEGREE || (multi_dt && ra.vdt == TGO_DT_INTEGER), 0};
     const uint64_t key_flip[2] = {
@@ -227,7 +228,7 @@ int encode_results(const ResultSource& src, const tgo_result_args* a, const int3
             lead[k] = reg[a->kind][k];                     // generic key: writeClassAndObject
         } else if (a->datatypes[k] != want[a->kind][k]) {
             err = "compute key datatype must be Long (distance), Double (pageRank, edgeCount, clustering coefficient), "
-                  "Integer (degree), Long or Integer (component, triangles) or generic (Object)";
+                  "Integer (degree), Long or Integer (component, triangles, core number) or generic (Object)";
             return TGO_E_UNSUPPORTED;
         }
     }

@@ -372,6 +372,25 @@ class Engine:
                                                                L.ptr(lcc, C.c_double)))
         return tri, deg, lcc
 
+    def kcore(self, fetch=True):
+        """k-core decomposition of a bothE load over its simple undirected projection (tgo_kcore):
+        (core, info) — core[v] = the largest k such that v lies in a subgraph whose vertices all
+        have at least k neighbours, in row order (None when fetch is False: the result stays on
+        the device for copy_cores / result_rows); info = dict(degeneracy, innermost, simple_edges,
+        levels, rounds).  rounds (peel launches) is a diagnostic and may differ run to run."""
+        a = L.CoreArgs(L.SCOPE_BOTH_E, 0)
+        info = L.CoreInfo()
+        out = np.zeros(self.n, dtype=np.int64) if fetch else None
+        _check(self.lib, self.ctx, self.lib.tgo_kcore(self.ctx, C.byref(a), L.ptr(out, C.c_int64), C.byref(info)))
+        return out, {"degeneracy": int(info.degeneracy), "innermost": int(info.innermost),
+                     "simple_edges": int(info.simple_edges), "levels": int(info.levels), "rounds": int(info.rounds)}
+
+    def copy_cores(self):
+        """The core numbers of the last kcore() run, in row order."""
+        out = np.zeros(self.n, dtype=np.int64)
+        _check(self.lib, self.ctx, self.lib.tgo_copy_cores(self.ctx, L.ptr(out, C.c_int64)))
+        return out
+
     def result_rows(self, kind, key_ids, datatypes, relation_id_base):
         """Edgestore entries of the last program's compute keys (tgo_result_rows): the rows
         ResultMode PERSIST writes back (FulgoraGraphComputer.java:248-305)."""
