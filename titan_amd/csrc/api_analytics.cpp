@@ -1,0 +1,386 @@
+// api_analytics.cpp — the analytics of a bothE load: connected components, triangles, k-core.
+#include "ctx.hpp"
+
+using namespace tgo;
+
+extern "C" {
+
+// ------------------------------------------------------------------ connected components
+// Weakly connected components (cc.hip).  Device arrays: parent = sc.level (int32), the per-root
+// minimum = sc.vec[0] (as int64), labels in internal order = sc.dist, row-order staging = sc.msg.
+// "changed" / "roots" words: Counters::qlen / red[0], read through the published mirror.
+static int cc_word(tgo_ctx* ctx, bool roots, unsigned long long& out) {
+    if (int rc = read_counters(ctx)) return rc;
+    out = roots ? ctx->sc.hcnt->red[0] : ctx->sc.hcnt->qlen;
+    return TGO_OK;
+}
+
+// Flatten the parent trees: pointer-jumping launches until one finds every vertex under a root.
+static int cc_compress(tgo_ctx* ctx, int32_t& rounds) {
+    Scratch& s = ctx->sc;
+    for (;;) {
+        HIP_TRY(k_level_prep(s.cnt, nullptr, 0, nullptr, ctx->stream));
+        {
+            DevSpan span(ctx->stream, "components.jump", {"round", rounds});
+            HIP_TRY(k_cc_jump(s.level, ctx->g.n, &s.cnt->qlen, ctx->stream));
+        }
+        ++rounds;
+        unsigned long long changed = 0;
+        if (int rc = cc_word(ctx, false, changed)) return rc;
+        if (!changed) return TGO_OK;
+    }
+}
+
+int tgo_components(tgo_ctx* ctx, const tgo_cc_args* a, int64_t* label_out, tgo_cc_info* info) {
+    int rc = bothE_program_check(ctx, a, "tgo_cc_args", "connected components run", nullptr);
+    if (rc) return rc;
+    DevGraph& g = ctx->g;
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    const int64_t n = g.n;
+    int64_t* const label = s.dist;
+    if (!g.cc_tid) {                // Titan id of every internal index: once per graph
+        HIP_TRY(dev_alloc(ctx, g.cc_tid, n));
+        ctx->st.device_bytes = ctx->dev_bytes;
+        HIP_TRY(hipMemcpyAsync(s.msg, ctx->titan_id.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(k_cc_scatter_ids(s.msg, g.perm, g.cc_tid, n, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    HIP_TRY(hipEventRecord(ctx->ev0, st));
+    int32_t rounds = 0;
+    const int path = g.has_transpose ? TGO_CC_PROPAGATE : TGO_CC_HOOK;
+    unsigned long long components = 0;
+    if (path == TGO_CC_HOOK) {
+        // every edge sits once in the OUT lists; the first entries are hooked and flattened
+        // first so that the bulk of the entries meets short trees
+        int32_t* const parent = s.level;
+        int64_t* const minid = reinterpret_cast<int64_t*>(s.vec[0]);
+        HIP_TRY(k_cc_init(parent, n, st));
+        {
+            DevSpan span(st, "components.hook_sample");
+            HIP_TRY(k_cc_hook(g.out, n, 0, 2, parent, st));
+            HIP_TRY(k_cc_hook(g.in, n, 0, 1, parent, st));
+        }
+        rounds += 2;
+        if ((rc = cc_compress(ctx, rounds))) return rc;
+        {
+            DevSpan span(st, "components.hook_rest");
+            HIP_TRY(k_cc_hook(g.out, n, 2, -1, parent, st));
+        }
+        ++rounds;
+        if ((rc = cc_compress(ctx, rounds))) return rc;
+        DevSpan span(st, "components.label");
+        HIP_TRY(k_fill_i64(minid, INT64_MAX, n, st));
+        HIP_TRY(k_level_prep(s.cnt, nullptr, 0, nullptr, st));
+        HIP_TRY(k_cc_min_id(parent, g.cc_tid, n, minid, st));
+        HIP_TRY(k_cc_label(parent, minid, n, label, &s.cnt->red[0], st));
+        span.end();
+        if ((rc = cc_word(ctx, true, components))) return rc;
+    } else {
+        const View pull = pull_view(g, TGO_SCOPE_BOTH_E);
+        HIP_TRY(hipMemcpyAsync(label, g.cc_tid, n * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        for (;;) {
+            HIP_TRY(k_level_prep(s.cnt, nullptr, 0, nullptr, st));
+            {
+                DevSpan span(st, "components.pull_round", {"round", rounds});
+                HIP_TRY(k_cc_pull_round(pull, n, label, &s.cnt->qlen, st));
+            }
+            ++rounds;
+            unsigned long long changed = 0;
+            if ((rc = cc_word(ctx, false, changed))) return rc;
+            if (!changed) break;
+        }
+        HIP_TRY(k_level_prep(s.cnt, nullptr, 0, nullptr, st));
+        HIP_TRY(k_cc_count_own(label, g.cc_tid, n, &s.cnt->red[0], st));
+        if ((rc = cc_word(ctx, true, components))) return rc;
+    }
+    if ((rc = program_end(ctx, rounds))) return rc;
+    if (info) *info = tgo_cc_info{static_cast<int64_t>(components), rounds, path};
+    if (label_out && (rc = rows_out(ctx, label, label_out))) return rc;
+    publish_result(ctx, TGO_RESULT_COMPONENT, ResultSource{label, nullptr});
+    return TGO_OK;
+}
+
+int tgo_copy_components(tgo_ctx* ctx, int64_t* label_out) {
+    if (!ctx || !label_out) return TGO_E_INVALID;
+    if (int rc = last_result_check(ctx, TGO_RESULT_COMPONENT, "tgo_components")) return rc;
+    // (unlike tgo_copy_triangles / tgo_copy_cores, no hipSetDevice first: the reason is unknown)
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return rows_out(ctx, ctx->sc.dist, label_out);
+}
+
+// ------------------------------------------------------------------ triangles
+// Triangle counting (tri.hip).  The forward lists, the degrees and the totals' words live with the
+// graph (dev_alloc: released with it); per run: counts in internal order = sc.dist, coefficients =
+// sc.vec[0], the block and wave kernels' row queues = sc.level and sc.q[0], row-order staging = sc.msg.
+// Defaults of TGO_TUNE_TRI_WAVE_ROW / _BLOCK_ROW (DESIGN.md 4.5 has the sweep).
+constexpr int64_t kTriWaveRow = 8, kTriBlockRow = 8;
+
+static int tri_forward_lists(tgo_ctx* ctx) {
+    DevGraph& g = ctx->g;
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    const int64_t n = g.n;
+    DevSpan span(st, "triangles.forward_lists");
+    AllocScope lists(ctx);          // the lists reach the graph all built, or a failure releases them all
+    unsigned long long* tot = nullptr;
+    int64_t *deg = nullptr, *foff = nullptr;
+    int32_t* fadj = nullptr;
+    HIP_TRY(dev_alloc(ctx, tot, 16));
+    HIP_TRY(dev_alloc(ctx, deg, n));
+    HIP_TRY(dev_alloc(ctx, foff, n + 1));
+    HIP_TRY(hipMemsetAsync(tot, 0, 16 * sizeof(unsigned long long), st));
+    // count, scan, fill: |fwd(v)| in sc.qdeg (n + 2)
+    HIP_TRY(k_tri_fwd_count(g.out, g.in, n, s.qdeg, deg, &tot[0], st));
+    HIP_TRY(scan_exclusive_i64(s.cub_tmp, s.cub_bytes, s.qdeg, foff, n + 1, st));
+    int64_t fnnz = 0;
+    unsigned long long longest = 0;
+    HIP_TRY(hipMemcpyAsync(&fnnz, foff + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&longest, tot, sizeof(longest), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (fnnz < 0 || fnnz > g.out.nnz + g.in.nnz) return fail(ctx, TGO_E_HIP, "forward lists: inconsistent entry count");
+    HIP_TRY(dev_alloc(ctx, fadj, fnnz));
+    HIP_TRY(k_tri_fwd_fill(g.out, g.in, n, foff, fadj, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    lists.commit();
+    g.tri_tot = tot;
+    g.tri_deg = deg;
+    g.tri_foff = foff;
+    g.tri_fadj = fadj;
+    g.tri_fnnz = fnnz;
+    g.tri_max_fwd = static_cast<int64_t>(longest);
+    ctx->st.device_bytes = ctx->dev_bytes;
+    return TGO_OK;
+}
+
+int tgo_triangles(tgo_ctx* ctx, const tgo_tri_args* a, int64_t* tri_out, tgo_tri_info* info) {
+    int rc = bothE_program_check(ctx, a, "tgo_tri_args", "triangles are counted", "triangles");
+    if (rc) return rc;
+    DevGraph& g = ctx->g;
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    const int64_t n = g.n;
+    if (!g.tri_fadj && (rc = tri_forward_lists(ctx))) return rc;
+    int64_t* const tri = s.dist;
+    double* const lcc = s.vec[0];
+    HIP_TRY(hipEventRecord(ctx->ev0, st));
+    HIP_TRY(k_fill_i64(tri, 0, n, st));
+    HIP_TRY(hipMemsetAsync(g.tri_tot + 1, 0, 15 * sizeof(unsigned long long), st));
+    {
+        DevSpan span(st, "triangles.count", {"forward_entries", g.tri_fnnz}, {"max_forward", g.tri_max_fwd});
+        HIP_TRY(k_tri_count(g.tri_foff, g.tri_fadj, n, tuned(ctx->tri_wave_row, kTriWaveRow),
+                            tuned(ctx->tri_block_row, kTriBlockRow), g.tri_max_fwd, tri, s.level,
+                            s.q[0], &g.tri_tot[5], st));
+    }
+    {
+        DevSpan span(st, "triangles.finish");
+        HIP_TRY(k_tri_finish(tri, g.tri_deg, n, lcc, g.tri_tot + 1, st));
+    }
+    unsigned long long tot[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(tot, g.tri_tot + 1, sizeof tot, hipMemcpyDeviceToHost, st));
+    if ((rc = program_end(ctx, 1))) return rc;
+    ctx->tri_max = static_cast<int64_t>(tot[3]);
+    if (info)
+        *info = tgo_tri_info{static_cast<int64_t>(tot[0] / 3), static_cast<int64_t>(tot[1]),
+                             static_cast<int64_t>(tot[2] / 2), g.tri_max_fwd};
+    if (tri_out && (rc = rows_out(ctx, tri, tri_out))) return rc;
+    publish_result(ctx, TGO_RESULT_TRIANGLES, ResultSource{tri, lcc});
+    return TGO_OK;
+}
+
+int tgo_copy_triangles(tgo_ctx* ctx, int64_t* tri_out, int64_t* deg_out, double* lcc_out) {
+    if (!ctx) return TGO_E_INVALID;
+    int rc = last_result_check(ctx, TGO_RESULT_TRIANGLES, "tgo_triangles");
+    if (rc) return rc;
+    (void)hipSetDevice(ctx->opts.device);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    // each copy-out finishes before the next reuses sc.msg
+    if (tri_out && (rc = rows_out(ctx, ctx->sc.dist, tri_out))) return rc;
+    if (deg_out && (rc = rows_out(ctx, ctx->g.tri_deg, deg_out))) return rc;
+    if (lcc_out && (rc = rows_out(ctx, ctx->sc.vec[0], lcc_out))) return rc;
+    return TGO_OK;
+}
+
+// ------------------------------------------------------------------ k-core decomposition
+// k-core (core.hip).  The backward lists and the totals' words live with the graph (dev_alloc:
+// released with it), beside the forward lists and degrees they share with tgo_triangles.  Per run:
+// working degrees (int32, the core numbers at the end) = sc.level, cores in internal order =
+// sc.dist, the alive lists = sc.q[0] / sc.q[1], the level queues = sc.vec[0] / sc.vec[1] (as
+// int32), row-order staging = sc.msg.  Level control: Counters through publish_turn / wait_publish.
+// Defaults of TGO_TUNE_CORE_WAVE_ROW / _TAIL / _LDS_QUEUE: DESIGN.md 4.6 has the sweep they come from.
+constexpr int64_t kCoreWaveRow = 64, kCoreTail = 1024, kCoreLdsQueue = 256;
+
+static int core_backward_lists(tgo_ctx* ctx) {
+    DevGraph& g = ctx->g;
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    const int64_t n = g.n;
+    DevSpan span(st, "kcore.lists", {"forward_entries", g.tri_fnnz});
+    AllocScope lists(ctx);          // all three arrays or none, as the forward lists
+    unsigned long long* tot = nullptr;
+    int64_t* boff = nullptr;
+    int32_t* badj = nullptr;
+    HIP_TRY(dev_alloc(ctx, tot, 2));
+    HIP_TRY(dev_alloc(ctx, boff, n + 1));
+    HIP_TRY(dev_alloc(ctx, badj, g.tri_fnnz));
+    // count, scan, fill: |bwd(v)| in sc.qdeg (n + 2), the fill's cursors in sc.qpre (n + 2)
+    HIP_TRY(hipMemsetAsync(s.qdeg, 0, (n + 1) * sizeof(int64_t), st));
+    HIP_TRY(k_core_bwd_count(g.tri_fadj, g.tri_fnnz, s.qdeg, st));
+    HIP_TRY(scan_exclusive_i64(s.cub_tmp, s.cub_bytes, s.qdeg, boff, n + 1, st));
+    HIP_TRY(hipMemcpyAsync(s.qpre, boff, (n + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    int64_t bnnz = -1;
+    HIP_TRY(hipMemcpyAsync(&bnnz, boff + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // (checked before the fill: its cursors stay inside badj only when the counts add up)
+    if (bnnz != g.tri_fnnz) return fail(ctx, TGO_E_HIP, "backward lists: inconsistent entry count");
+    HIP_TRY(k_core_bwd_fill(g.tri_foff, g.tri_fadj, n, s.qpre, badj, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    lists.commit();
+    g.core_tot = tot;
+    g.core_boff = boff;
+    g.core_badj = badj;
+    ctx->st.device_bytes = ctx->dev_bytes;
+    return TGO_OK;
+}
+
+// One publish of the level counters, which are zero again afterwards.
+static int core_turn(tgo_ctx* ctx) {
+    Scratch& s = ctx->sc;
+    const unsigned long long seq = ++s.pub_seq;
+    HIP_TRY(k_publish_turn(s.cnt, s.hcnt_dev, seq, nullptr, ctx->stream));
+    int rc = wait_publish(ctx, seq);
+    if (rc) return rc;
+    if (s.hcnt->err) return fail(ctx, TGO_E_HIP, "k-core peel: a queue overflowed (inconsistent lists)");
+    return TGO_OK;
+}
+
+// The peel: deg (a copy of d(v)) ends as the core numbers.  Out: levels, peel launches, the largest
+// core number and the vertices peeled at it.
+static int core_peel_levels(tgo_ctx* ctx, int32_t* deg, int32_t& levels, int32_t& rounds, int64_t& top,
+                            int64_t& innermost) {
+    DevGraph& g = ctx->g;
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    const int64_t n = g.n;
+    const CoreView lists{g.tri_foff, g.tri_fadj, g.core_boff, g.core_badj};
+    const int64_t wave_row = tuned(ctx->core_wave_row, kCoreWaveRow);
+    const int64_t tail = std::min<int64_t>(tuned(ctx->core_tail, kCoreTail), kCoreQueue);
+    const int64_t lds_cap = tuned(ctx->core_lds_queue, kCoreLdsQueue);
+    int32_t* const alive_list[2] = {s.q[0], s.q[1]};
+    int32_t* const queue[2] = {reinterpret_cast<int32_t*>(s.vec[0]), reinterpret_cast<int32_t*>(s.vec[1])};
+    auto min_of = [](unsigned long long word) {        // Counters::red[0] of core_scan / core_peel
+        return word ? static_cast<int64_t>(INT32_MAX) - static_cast<int64_t>(word) : INT64_MAX;
+    };
+    int rc = TGO_OK;
+    HIP_TRY(k_core_deg_init(g.tri_deg, n, deg, st));
+    HIP_TRY(k_level_prep(s.cnt, nullptr, 0, nullptr, st));
+    // the smallest degree: a scan that queues nothing
+    HIP_TRY(k_core_scan(nullptr, n, deg, -1, nullptr, nullptr, s.cnt, st));
+    if ((rc = core_turn(ctx))) return rc;
+    int64_t next_k = min_of(s.hcnt->red[0]);
+    int64_t alive = n, len = n, k = -1;
+    const int32_t* list = nullptr;      // the alive list in use (null: every vertex)
+    int spare = 0;                      // the alive_list buffer it is not in
+    while (alive > 0) {
+        if (next_k == INT64_MAX) return fail(ctx, TGO_E_HIP, "k-core peel: alive vertices without a degree");
+        if (tail > 0 && alive <= tail) {
+            if (len > 2 * alive) {      // the one workgroup scans the list once per level: compact it first
+                HIP_TRY(k_core_scan(list, len, deg, static_cast<int32_t>(k), nullptr, alive_list[spare], s.cnt, st));
+                if ((rc = core_turn(ctx))) return rc;
+                list = alive_list[spare];
+                spare ^= 1;
+                len = static_cast<int64_t>(s.hcnt->mf);
+                if (len != alive) return fail(ctx, TGO_E_HIP, "k-core peel: inconsistent alive count");
+            }
+            HIP_TRY(k_core_tail(list, len, lists, deg, static_cast<int32_t>(k), wave_row, s.cnt, st));
+            if ((rc = core_turn(ctx))) return rc;
+            ++rounds;
+            levels += static_cast<int32_t>(s.hcnt->qlen);
+            innermost = static_cast<int64_t>(s.hcnt->mf);
+            top = static_cast<int64_t>(s.hcnt->red[0]);
+            return TGO_OK;
+        }
+        k = next_k;
+        const bool rebuild = 2 * alive <= len;      // the list has at least halved
+        HIP_TRY(k_core_scan(list, len, deg, static_cast<int32_t>(k), queue[0], rebuild ? alive_list[spare] : nullptr,
+                            s.cnt, st));
+        if ((rc = core_turn(ctx))) return rc;
+        int64_t qlen = static_cast<int64_t>(s.hcnt->qlen);
+        next_k = min_of(s.hcnt->red[0]);
+        if (rebuild) {
+            list = alive_list[spare];
+            spare ^= 1;
+            len = static_cast<int64_t>(s.hcnt->mf);
+        }
+        // the minimum named a vertex that the level before went on to drop and peel: nobody is
+        // left at k, and this scan's minimum is exact (nothing has changed since it ran)
+        if (qlen == 0) continue;
+        if (qlen > alive) return fail(ctx, TGO_E_HIP, "k-core peel: inconsistent level queue");
+        ++levels;
+        top = k;
+        innermost = qlen;
+        alive -= qlen;
+        for (int cur = 0; qlen > 0 && k > 0; cur ^= 1) {    // (a vertex of level 0 has no neighbour)
+            HIP_TRY(k_core_peel(queue[cur], qlen, lists, deg, static_cast<int32_t>(k), wave_row, lds_cap, queue[cur ^ 1],
+                                n, s.cnt, st));
+            if ((rc = core_turn(ctx))) return rc;
+            ++rounds;
+            const int64_t drops = static_cast<int64_t>(s.hcnt->mf);     // queued for the next launch or not
+            qlen = static_cast<int64_t>(s.hcnt->qlen);
+            if (drops > alive || qlen > drops) return fail(ctx, TGO_E_HIP, "k-core peel: inconsistent drop count");
+            innermost += drops;
+            alive -= drops;
+            next_k = std::min(next_k, min_of(s.hcnt->red[0]));
+        }
+    }
+    return TGO_OK;
+}
+
+int tgo_kcore(tgo_ctx* ctx, const tgo_core_args* a, int64_t* core_out, tgo_core_info* info) {
+    int rc = bothE_program_check(ctx, a, "tgo_core_args", "core numbers are computed", "core numbers");
+    if (rc) return rc;
+    DevGraph& g = ctx->g;
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    const int64_t n = g.n;
+    if (!g.tri_fadj && (rc = tri_forward_lists(ctx))) return rc;
+    if (!g.core_badj && (rc = core_backward_lists(ctx))) return rc;
+    int32_t* const deg = s.level;
+    int64_t* const core = s.dist;
+    HIP_TRY(hipEventRecord(ctx->ev0, st));
+    int32_t levels = 0, rounds = 0;
+    int64_t top = 0, innermost = 0;
+    unsigned long long tot[2] = {0, 0};
+    if (g.tri_fnnz == 0) {
+        // no simple edge: nothing is peeled, every core number is 0 and the info stays zero
+        HIP_TRY(k_fill_i64(core, 0, n, st));
+    } else {
+        {
+            DevSpan span(st, "kcore.peel", {"simple_edges", g.tri_fnnz});
+            if ((rc = core_peel_levels(ctx, deg, levels, rounds, top, innermost))) return rc;
+        }
+        DevSpan span(st, "kcore.finish");
+        HIP_TRY(hipMemsetAsync(g.core_tot, 0, 2 * sizeof(unsigned long long), st));
+        HIP_TRY(k_core_finish(deg, n, static_cast<int32_t>(top), core, g.core_tot, st));
+        span.end();
+        HIP_TRY(hipMemcpyAsync(tot, g.core_tot, sizeof tot, hipMemcpyDeviceToHost, st));
+    }
+    if ((rc = program_end(ctx, levels))) return rc;
+    // the device's own count of the result against the level loop's bookkeeping
+    if (static_cast<int64_t>(tot[1]) != top || static_cast<int64_t>(tot[0]) != innermost)
+        return fail(ctx, TGO_E_HIP, "k-core: the core numbers disagree with the peel's level counts");
+    if (info) *info = tgo_core_info{top, innermost, g.tri_fnnz, levels, rounds};
+    if (core_out && (rc = rows_out(ctx, core, core_out))) return rc;
+    publish_result(ctx, TGO_RESULT_CORE, ResultSource{core, nullptr});
+    return TGO_OK;
+}
+
+int tgo_copy_cores(tgo_ctx* ctx, int64_t* core_out) {
+    if (!ctx || !core_out) return TGO_E_INVALID;
+    if (int rc = last_result_check(ctx, TGO_RESULT_CORE, "tgo_kcore")) return rc;
+    (void)hipSetDevice(ctx->opts.device);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return rows_out(ctx, ctx->sc.dist, core_out);
+}
+
+}  // extern "C"

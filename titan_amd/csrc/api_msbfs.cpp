@@ -397,14 +397,8 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
     }
     if (qlen > 0 && a->max_depth > depth)
         return fail(ctx, TGO_E_UNSUPPORTED, "multi-source BFS stores levels as uint16: depth > 65534");
-    HIP_TRY(hipEventRecord(ctx->ev1, st));
-    HIP_TRY(hipEventSynchronize(ctx->ev1));
-    trace_resolve(st);
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->st.last_kernel_ms = ms;
+    if (int rc = program_end(ctx, a->max_depth)) return rc;
     ctx->st.levels = levels;
-    ctx->st.iterations = a->max_depth;
     // the last level was sparse and found nothing: its frontier's masks are cleared, nothing was
     // written to the other buffer; ms_fr's entry-less tail (seeds only) was cleared at level 0
     s.ms_masks_zero = level0_sparse && last_sparse && qlen == 0;

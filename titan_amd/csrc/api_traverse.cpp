@@ -472,27 +472,20 @@ int run_delta(tgo_ctx* ctx, int64_t seed, int scope, bool weighted, int64_t delt
 }
 
 int finish_distance_program(tgo_ctx* ctx, int scope, int flags, int64_t* dist_out) {
-    Scratch& s = ctx->sc;
+    // not program_end: the loops set the iterations, and run_bfs, run_sssp and the device delta
+    // loop resolve the trace themselves (run_delta's scan loop never does: the reason is unknown)
     HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
     HIP_TRY(hipEventSynchronize(ctx->ev1));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->st.last_kernel_ms = ms;
+    int rc = program_elapsed(ctx);
+    if (rc) return rc;
     if (flags & TGO_FLAG_STATS) {
-        // reached vertices and the entries of their pull lists (both lists for bothE)
-        HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), ctx->stream));
-        HIP_TRY(k_reach_stats(pull_view(ctx->g, scope), s.dist, ctx->g.n, s.cnt->red, ctx->stream));
-        int rc = read_counters(ctx);
-        if (rc) return rc;
-        ctx->st.reached = static_cast<int64_t>(s.hcnt->red[0]);
-        ctx->st.reached_entries = static_cast<int64_t>(s.hcnt->red[1]);
+        int64_t reached[2];
+        if ((rc = reach_stats(ctx, scope, reached))) return rc;
+        ctx->st.reached = reached[0];
+        ctx->st.reached_entries = reached[1];
     }
-    if (dist_out) {
-        HIP_TRY(k_unpermute_i64(s.dist, ctx->g.perm, s.msg, ctx->g.n, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(dist_out, s.msg, ctx->g.n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-    }
-    (void)scope;
+    if (dist_out && (rc = rows_out(ctx, ctx->sc.dist, dist_out))) return rc;
+    publish_result(ctx, TGO_RESULT_DISTANCE, ResultSource{ctx->sc.dist, nullptr});
     return TGO_OK;
 }
 
@@ -512,11 +505,7 @@ int tgo_bfs(tgo_ctx* ctx, const tgo_bfs_args* a, int64_t* dist_out) {
     if ((rc = resolve_seed(ctx, a->seed, a->seed_is_dense, seed))) return rc;
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
     if ((rc = run_bfs(ctx, seed, a->max_depth, a->scope))) return rc;
-    if ((rc = finish_distance_program(ctx, a->scope, a->flags, dist_out))) return rc;
-    ctx->res_kind = TGO_RESULT_DISTANCE;
-    ctx->res_empty = false;
-    ctx->res_src = ResultSource{ctx->sc.dist, nullptr};
-    return TGO_OK;
+    return finish_distance_program(ctx, a->scope, a->flags, dist_out);
 }
 
 int tgo_sssp(tgo_ctx* ctx, const tgo_sssp_args* a, int64_t* dist_out) {
@@ -545,21 +534,15 @@ int tgo_sssp(tgo_ctx* ctx, const tgo_sssp_args* a, int64_t* dist_out) {
     } else {
         if ((rc = run_sssp(ctx, seed, a->max_depth, a->scope, ctx->g.has_weight))) return rc;
     }
-    if ((rc = finish_distance_program(ctx, a->scope, a->flags, dist_out))) return rc;
-    ctx->res_kind = TGO_RESULT_DISTANCE;
-    ctx->res_empty = false;
-    ctx->res_src = ResultSource{ctx->sc.dist, nullptr};
-    return TGO_OK;
+    return finish_distance_program(ctx, a->scope, a->flags, dist_out);
 }
 
+// (no last_result_check: PageRank's ranks are fetched through this too, from the same scratch)
 int tgo_copy_distances(tgo_ctx* ctx, int64_t* dist_out) {
     if (!ctx || !dist_out) return TGO_E_INVALID;
     if (!ctx->loaded) return fail(ctx, TGO_E_STATE, "no graph loaded");
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(k_unpermute_i64(ctx->sc.dist, ctx->g.perm, ctx->sc.msg, ctx->g.n, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dist_out, ctx->sc.msg, ctx->g.n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return TGO_OK;
+    return rows_out(ctx, ctx->sc.dist, dist_out);
 }
 
 }  // extern "C"

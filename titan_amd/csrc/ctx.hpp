@@ -1,6 +1,6 @@
 // ctx.hpp — the context behind the C-ABI's opaque tgo_ctx, and the helpers that the driver
-// files (api.cpp, api_traverse.cpp, api_msbfs.cpp, part_driver.cpp) share.  A function used by
-// more than one of them is declared here, once.  Private to titan_amd/csrc: never installed.
+// files (api*.cpp, part_driver.cpp) share: a function used by more than one of them is declared here,
+// once, under its file's heading; program.hpp (included last) is the frame of a program driver.  Private.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -202,7 +202,8 @@ inline int scan_frontier(tgo_ctx* ctx, int64_t qlen) {
     return TGO_OK;
 }
 
-// The partitioned primitives (api.cpp) open and close with these three.
+// ------------------------------------------------------------------ api_part.cpp
+// The partitioned primitives open and close with these three.
 inline int part_check(tgo_ctx* ctx) {
     if (!ctx) return TGO_E_INVALID;
     if (!ctx->loaded || !ctx->g.partitioned) return fail(ctx, TGO_E_STATE, "no partitioned graph loaded");
@@ -240,10 +241,6 @@ inline int part_counts(tgo_ctx* ctx, int64_t* counts, bool device_ok = true) {
 }
 
 // ... and what part_driver.cpp's loops call between them
-int part_upload(tgo_ctx* ctx, HostGraph& h, int64_t n_global, int64_t lo);
-int part_rows_take(tgo_ctx* ctx, RowStaging& st, std::string& err);
-// a failed row load: the staged rows and the decoder's buffers go together
-void part_drop_staging(tgo_ctx* ctx);
 int part_dims(tgo_ctx* ctx, int64_t* n_local, int64_t* lo, int64_t* n_global, int64_t* entries);
 int part_scratch(tgo_ctx* ctx, void** p, int64_t bytes, int slot);
 // this rank's slice of the candidate words bypasses the pack / exchange (ORed in directly by the
@@ -266,6 +263,21 @@ int part_sssp_split(tgo_ctx* ctx, int64_t delta, bool* on);
 int part_sssp_dev_relax(tgo_ctx* ctx, int32_t nranks, int64_t* send, int64_t* sizes, int64_t* fold);
 int part_sssp_dev_apply(tgo_ctx* ctx, const int64_t* recv, int64_t npairs);
 int part_sssp_dev_extract(tgo_ctx* ctx, int64_t thr);
+
+// ------------------------------------------------------------------ api_load.cpp
+struct TrimTemps { ~TrimTemps() { tmp_trim(); } };     // tmp_cache.cpp: nothing stays reserved between loads
+int64_t pr_hot_default();
+int upload_cold_blocks(tgo_ctx* ctx, const std::vector<int64_t>& off, const std::vector<int32_t>& adj,
+                       int64_t n_src, int64_t hot, int64_t n_rows, ColdBlocks& cb, bool& ready,
+                       const int64_t* d_off = nullptr, const int32_t* d_adj = nullptr, int64_t d_nnz = 0,
+                       int64_t win = 0);
+int part_upload(tgo_ctx* ctx, HostGraph& h, int64_t n_global, int64_t lo);
+int part_rows_take(tgo_ctx* ctx, RowStaging& st, std::string& err);
+// a failed row load: the staged rows and the decoder's buffers go together
+void part_drop_staging(tgo_ctx* ctx);
+
+// ------------------------------------------------------------------ api_pagerank.cpp
+int fx_take_bad(tgo_ctx* ctx, ColdBlocks& cb, bool* bad);
 
 // ------------------------------------------------------------------ api_traverse.cpp
 int64_t default_delta(const DevGraph& g, bool weighted);
@@ -293,3 +305,5 @@ inline int ms_planes_for(tgo_ctx* ctx, int32_t level) {
 }
 
 }  // namespace tgo
+
+#include "program.hpp"

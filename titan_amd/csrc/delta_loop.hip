@@ -771,7 +771,7 @@ __global__ void __launch_bounds__(kBlock) ds_relax_dev(const int64_t* __restrict
 }
 
 // ---------------------------------------------------------------- 1-D partition
-// The partitioned loop (part_driver.cpp tgo_part_sssp_run over api.cpp's part_sssp_dev_*) runs
+// The partitioned loop (part_driver.cpp tgo_part_sssp_run over api_part.cpp's part_sssp_dev_*) runs
 // this file's commit / relax / extraction on each rank's rows; the decisions are global, so
 // they come from the host after the per-phase header exchange instead of ds_decide.
 //

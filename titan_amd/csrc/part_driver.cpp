@@ -304,7 +304,7 @@ const char* tgo_exchange_last_error(const tgo_exchange* x) { return x ? x->err.c
 
 namespace tgo {
 
-// part_scratch (api.cpp) for an array of `count` T
+// part_scratch (api_part.cpp) for an array of `count` T
 template <class T>
 int scratch(tgo_ctx* ctx, T*& p, int64_t count, int slot) {
     void* q = nullptr;
