@@ -370,11 +370,19 @@ int  tgo_copy_multi_distances(tgo_ctx* ctx, int32_t source, int64_t* dist_out);
  * TGO_TUNE_CORE_LDS_QUEUE: the vertices a workgroup's own queue holds, in [1, 4096]: what a
  * workgroup drops it peels itself from that queue, and only what does not fit goes to the next
  * launch.  For all three < 0 = the default, and every value gives the same core numbers. */
+/* TGO_TUNE_SCC_WAVE_ROW (tgo_scc): a row of at least this many entries is walked by its whole wave
+ * instead of its own lane; an integer >= 1.
+ * TGO_TUNE_SCC_TAIL: once at most this many vertices are without a component, one workgroup finishes
+ * every remaining pass inside one launch (at most 4096: larger values mean 4096); 0 = never.
+ * TGO_TUNE_SCC_TRIM / TGO_TUNE_SCC_PIVOT: 0 = the trim / the pivot's forward-backward reach is
+ * skipped and the later phases do its work (for tests), 1 = it runs.  For all four < 0 = the
+ * default, and every value gives the same labels. */
 enum { TGO_TUNE_MS_SPLIT = 1, TGO_TUNE_MS_GHOST = 2, TGO_TUNE_DS_BINS = 3, TGO_TUNE_DS_PILE_CAP = 4,
        TGO_TUNE_DS_DONE = 5, TGO_TUNE_MS_COLD = 6, TGO_TUNE_DS_PULL = 7, TGO_TUNE_DS_SMALL = 8,
        TGO_TUNE_MS_STAY = 9, TGO_TUNE_MS_SPARSE = 10, TGO_TUNE_TRI_WAVE_ROW = 11,
        TGO_TUNE_TRI_BLOCK_ROW = 12, TGO_TUNE_MS_HEAD = 13, TGO_TUNE_CORE_WAVE_ROW = 14,
-       TGO_TUNE_CORE_TAIL = 15, TGO_TUNE_CORE_LDS_QUEUE = 16 };
+       TGO_TUNE_CORE_TAIL = 15, TGO_TUNE_CORE_LDS_QUEUE = 16, TGO_TUNE_SCC_WAVE_ROW = 17,
+       TGO_TUNE_SCC_TAIL = 18, TGO_TUNE_SCC_TRIM = 19, TGO_TUNE_SCC_PIVOT = 20 };
 int  tgo_set_tuning(tgo_ctx* ctx, int32_t key, double value);
 
 /* ---- Tracing (the reference's only hook is FulgoraGraphComputer.java:143,307
@@ -469,6 +477,35 @@ typedef struct { int32_t scope; int32_t flags; } tgo_core_args;
 typedef struct { int64_t degeneracy, innermost, simple_edges; int32_t levels, rounds; } tgo_core_info;
 int  tgo_kcore(tgo_ctx* ctx, const tgo_core_args* args, int64_t* core_out, tgo_core_info* info);
 int  tgo_copy_cores(tgo_ctx* ctx, int64_t* core_out);
+
+/* ---- Strongly connected components -----------------------------------------------------
+ * Over the directed graph of a bothE load: an arc u -> v iff an OUT entry of u names v, which is
+ * to say an IN entry of v names u.  Parallel arcs change nothing; neither does a self-loop (a vertex
+ * whose only cycle is its self-loop is a component of one); a vertex cut counts as its canonical
+ * vertex; a vertex without entries is its own component.  Per vertex in row order:
+ *   label[v]  the smallest Titan id among the vertices w such that v reaches w and w reaches v
+ *             (v included); Titan ids are compared, not internal ids, as in tgo_components
+ * The partition and its labels are unique: results are bit-identical run to run and for every
+ * TGO_TUNE_SCC_* value.  info:
+ *   components  distinct labels; deterministic
+ *   largest     vertices of the largest component; deterministic
+ *   singletons  components of one vertex; deterministic
+ *   rounds      device launches of the trim, reach and colouring loops; also tgo_stats.iterations
+ *   passes      colouring passes
+ * rounds and passes are DIAGNOSTICS: they may differ between runs and between tuning values (which
+ * workgroup discovers a vertex decides whether the next launch or the same one walks it).
+ * n = 0 or a graph without any entry: every vertex is its own label, components = singletons = n,
+ * largest = min(n, 1), rounds = passes = 0.
+ * args->scope must be TGO_SCOPE_BOTH_E and the loaded scope (else TGO_E_INVALID), args->flags 0.
+ * Lists that are not each other's transpose (tgo_load_csr with asymmetric rows): TGO_E_UNSUPPORTED
+ * (forward along OUT and backward along IN would walk two different graphs); so does a partitioned
+ * ctx.  A failed call leaves the ctx usable.  label_out NULL: the labels stay on the device
+ * (tgo_copy_scc; tgo_result_rows kind TGO_RESULT_SCC).  Nothing is cached with the graph but the
+ * Titan ids by internal index that tgo_components shares (8 n bytes, tgo_stats.device_bytes). */
+typedef struct { int32_t scope; int32_t flags; } tgo_scc_args;
+typedef struct { int64_t components, largest, singletons; int32_t rounds, passes; } tgo_scc_info;
+int  tgo_scc(tgo_ctx* ctx, const tgo_scc_args* args, int64_t* label_out, tgo_scc_info* info);
+int  tgo_copy_scc(tgo_ctx* ctx, int64_t* label_out);
 
 /* ---- Generic vertex programs ----------------------------------------
  * A vertex program the engine does not implement natively runs its execute() on the host
@@ -578,6 +615,7 @@ int  tgo_dense_ids(tgo_ctx* ctx, const int64_t* titan_ids, int64_t count, int64_
  *             executed vertex
  *   CORE      tgo_kcore's core number (Long, or Integer: a core number is at most d(v) < 2^31) on
  *             every executed vertex; any other typed key: TGO_E_INVALID
+ *   SCC       tgo_scc's label, encoded exactly as COMPONENT
  * Compute keys are typed property keys of those datatypes, or generic keys (TGO_DT_OBJECT: what
  * getOrCreatePropertyKey makes for a key the program sets without a schema, DefaultSchemaMaker
  * .java:46-48), whose values carry their class (Long 13, Double 20, Integer 12).  Relation ids are
@@ -587,11 +625,11 @@ int  tgo_dense_ids(tgo_ctx* ctx, const int64_t* titan_ids, int64_t count, int64_
  * (the tgo_rows layout, so the rows can be scanned again). */
 typedef enum { TGO_RESULT_DISTANCE = 0, TGO_RESULT_PAGERANK = 1, TGO_RESULT_DEGREE = 2,
                TGO_RESULT_VALUES = 3, TGO_RESULT_COMPONENT = 4, TGO_RESULT_TRIANGLES = 5,
-               TGO_RESULT_CORE = 6 } tgo_result_kind;
+               TGO_RESULT_CORE = 6, TGO_RESULT_SCC = 7 } tgo_result_kind;
 typedef struct {
     int32_t kind;                 /* tgo_result_kind                                          */
     int32_t reserved;             /* TGO_RESULT_VALUES: tgo_value_type of the values           */
-    int64_t key_ids[2];           /* [0] DISTANCE / PAGE_RANK / DEGREE / COMPONENT / TRIANGLES / CORE key; [1] OUTGOING_EDGE_COUNT / CLUSTERING */
+    int64_t key_ids[2];           /* [0] DISTANCE / PAGE_RANK / DEGREE / COMPONENT / TRIANGLES / CORE / SCC key; [1] OUTGOING_EDGE_COUNT / CLUSTERING */
     int32_t datatypes[2];         /* tgo_datatype of each key                                  */
     int64_t relation_id_base;
 } tgo_result_args;

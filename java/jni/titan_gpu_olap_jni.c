@@ -316,6 +316,21 @@ JNIEXPORT jlongArray JNICALL JFN(kcore)(JNIEnv* env, jclass cls, jlong h) {
     return distances(env, h, run_kcore, &a);
 }
 
+/* tgo_scc over the bothE load read as a directed graph: every vertex's component label (the smallest
+ * Titan id of its strongly connected component) in row order, or NULL on error (the device launches
+ * are tgo_stats.iterations afterwards; write-back: tgo_result_rows kind TGO_RESULT_SCC). */
+static int run_scc(tgo_ctx* c, const void* a, int64_t* o) {
+    return tgo_scc(c, (const tgo_scc_args*)a, o, NULL);
+}
+
+JNIEXPORT jlongArray JNICALL JFN(scc)(JNIEnv* env, jclass cls, jlong h) {
+    (void)cls;
+    tgo_scc_args a;
+    memset(&a, 0, sizeof a);
+    a.scope = TGO_SCOPE_BOTH_E;
+    return distances(env, h, run_scc, &a);
+}
+
 /* tgo_result_rows: Object[5] = {long[] rowKeys, long[] rowEntryBegin, long[] rowByteBegin,
  * long[] entryLimitValuePos, byte[] entryBytes}, or NULL on error (status: lastError; a result
  * beyond the int32 index range of a Java array: IllegalStateException). */

@@ -46,7 +46,8 @@ import java.util.concurrent.Future;
  * storeState(), or the DegreeCounter's length field), and a ConnectedComponentVertexProgram
  * (weakly connected components over bothE, tgo_components), a TriangleCountVertexProgram
  * (triangles and clustering coefficients of the simple undirected projection, tgo_triangles) and
- * a KCoreVertexProgram (core numbers of the same projection, tgo_kcore).
+ * a KCoreVertexProgram (core numbers of the same projection, tgo_kcore),
+ * a StronglyConnectedComponentsVertexProgram (bothE read as a directed graph, tgo_scc).
  *
  * Write-back (FulgoraGraphComputer.java:248-305): with Persist.VERTEX_PROPERTIES the compute
  * keys are encoded on the device (tgo_result_rows: single-cardinality property entries, one
@@ -543,6 +544,8 @@ public class GpuGraphComputer implements TitanGraphComputer {
                     return new TriangleCount();
                 case "com.thinkaurelius.titan.olap.KCoreVertexProgram":
                     return new KCore();
+                case "com.thinkaurelius.titan.olap.StronglyConnectedComponentsVertexProgram":
+                    return new StronglyConnectedComponents();
                 default:
                     throw new TitanException("vertex program " + p.getClass().getName() + " is not supported on the GPU path");
             }
@@ -736,6 +739,31 @@ public class GpuGraphComputer implements TitanGraphComputer {
         }
         void emit(long[] ids, Map<String, Object> values, FulgoraMapEmitter emitter) {
             long[] c = (long[]) values.get(CORE);
+            for (int i = 0; i < ids.length; i++) emitter.emit(ids[i], c[i]);
+        }
+    }
+
+    /**
+     * Strongly connected components over bothE read as a directed graph (tgo_scc): COMPONENT = the
+     * smallest Titan id among the vertices that the vertex reaches and that reach it.  The iteration
+     * reported is the number of device launches of the run, known after run().
+     */
+    static final class StronglyConnectedComponents extends DeviceProgram {
+        static final String COMPONENT = "titan.scc.component";
+        private int rounds;
+        int scope() { return TgoNative.SCOPE_BOTH_E; }
+        int iterations() { return rounds; }
+        int resultKind() { return TgoNative.RESULT_SCC; }
+        String[] computeKeys() { return new String[]{COMPONENT}; }
+        int[] computeKeyTypes() { return new int[]{TgoNative.DT_LONG}; }
+        Map<String, Object> run(long ctx) {
+            Map<String, Object> v = new HashMap<>();
+            v.put(COMPONENT, TgoNative.checked(ctx, TgoNative.scc(ctx)));
+            rounds = (int) TgoNative.stats(ctx)[3];
+            return v;
+        }
+        void emit(long[] ids, Map<String, Object> values, FulgoraMapEmitter emitter) {
+            long[] c = (long[]) values.get(COMPONENT);
             for (int i = 0; i < ids.length; i++) emitter.emit(ids[i], c[i]);
         }
     }

@@ -95,12 +95,19 @@ public final class TgoNative {
      */
     public static native long[] kcore(long ctx);
 
+    /**
+     * tgo_scc over a bothE load read as a directed graph: every vertex's label, the smallest Titan
+     * id of its strongly connected component, in row order; null on failure.  stats()[3] then holds
+     * the device launches of the run.
+     */
+    public static native long[] scc(long ctx);
+
     /** tgo_stats_get: {ghostVertices, truncatedResults, skippedRows, iterations, loadMs, lastKernelMs}. */
     public static native double[] stats(long ctx);
 
     /** tgo_result_kind */
     public static final int RESULT_DISTANCE = 0, RESULT_PAGERANK = 1, RESULT_DEGREE = 2, RESULT_COMPONENT = 4,
-            RESULT_TRIANGLES = 5, RESULT_CORE = 6;
+            RESULT_TRIANGLES = 5, RESULT_CORE = 6, RESULT_SCC = 7;
     /**
      * tgo_result_rows: the edgestore entries (single-cardinality property entries) of the last
      * program's compute keys, as {long[] rowKeys, long[] rowEntryBegin, long[] rowByteBegin,

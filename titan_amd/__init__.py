@@ -9,8 +9,8 @@ from .computer import (  # noqa: F401
     ClusterCountMapReduce, ClusterPopulationMapReduce, ConnectedComponentVertexProgram, CoreSizeMapReduce,
     DegeneracyMapReduce, DegreeCounter, DegreeMapper, ExecutionException, GpuGraph, GpuGraphComputer,
     KCoreVertexProgram, KeyValue,
-    PageRankMapReduce, PageRankVertexProgram, ShortestDistanceMapReduce,
-    ShortestDistanceVertexProgram, TitanGraphComputer, TransitivityMapReduce, TriangleCountMapReduce,
+    PageRankMapReduce, PageRankVertexProgram, SccSizeMapReduce, ShortestDistanceMapReduce,
+    ShortestDistanceVertexProgram, StronglyConnectedComponentsVertexProgram, TitanGraphComputer, TransitivityMapReduce, TriangleCountMapReduce,
     TriangleCountVertexProgram,
 )
 from .generic import (  # noqa: F401
@@ -28,4 +28,5 @@ __all__ = [
     "ConnectedComponentVertexProgram", "ClusterPopulationMapReduce", "ClusterCountMapReduce",
     "TriangleCountVertexProgram", "TriangleCountMapReduce", "TransitivityMapReduce",
     "KCoreVertexProgram", "DegeneracyMapReduce", "CoreSizeMapReduce",
+    "StronglyConnectedComponentsVertexProgram", "SccSizeMapReduce",
 ]

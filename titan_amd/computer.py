@@ -421,6 +421,26 @@ class KCoreVertexProgram(VertexProgram):
         return KCoreVertexProgram.Builder()
 
 
+class StronglyConnectedComponentsVertexProgram(VertexProgram):
+    """Strongly connected components over bothE read as a directed graph (tgo_scc): an arc u -> v
+    for every OUT edge of u to v.  COMPONENT = the smallest Titan id among the vertices that the
+    vertex reaches and that reach it (Long); parallel edges and self-loops change nothing.
+    memory.getIteration() reports the device launches of the trim, reach and colouring loops, not
+    the supersteps a colouring vertex program would take.  Result graph and persist preference as
+    ShortestDistanceVertexProgram."""
+    COMPONENT = "titan.scc.component"
+    compute_keys = (COMPONENT,)
+    scope_name = "bothE"
+
+    class Builder:
+        def create(self, graph=None):
+            return StronglyConnectedComponentsVertexProgram()
+
+    @staticmethod
+    def build():
+        return StronglyConnectedComponentsVertexProgram.Builder()
+
+
 # ----------------------------------------------------------------------------- map-reduces
 class MapReduce:
     memory_key = ""
@@ -604,6 +624,25 @@ class CoreSizeMapReduce(MapReduce):
         return {int(k): int(v) for k, v in zip(u, c)}
 
 
+class SccSizeMapReduce(MapReduce):
+    """Strongly connected component label -> number of vertices carrying it."""
+    DEFAULT_MEMORY_KEY = "sccSizes"
+
+    def __init__(self, key=DEFAULT_MEMORY_KEY):
+        self.memory_key = key
+
+    @staticmethod
+    def build():
+        return _MemoryKeyBuilder(SccSizeMapReduce)
+
+    def emit(self, ids, props):
+        lab = props.get(StronglyConnectedComponentsVertexProgram.COMPONENT)
+        if lab is None:
+            return {}
+        u, c = np.unique(np.asarray(lab, dtype=np.int64), return_counts=True)
+        return {int(k): int(v) for k, v in zip(u, c)}
+
+
 class DegreeMapper(MapReduce):
     DEGREE_RESULT = "degrees"                 # OLAPTest.java:420
     memory_key = DEGREE_RESULT
@@ -729,7 +768,9 @@ class GpuGraphComputer(TitanGraphComputer):
                     ConnectedComponentVertexProgram: (L.RESULT_COMPONENT, (ConnectedComponentVertexProgram.COMPONENT,)),
                     TriangleCountVertexProgram: (L.RESULT_TRIANGLES, (TriangleCountVertexProgram.TRIANGLES,
                                                                       TriangleCountVertexProgram.CLUSTERING)),
-                    KCoreVertexProgram: (L.RESULT_CORE, (KCoreVertexProgram.CORE,))}
+                    KCoreVertexProgram: (L.RESULT_CORE, (KCoreVertexProgram.CORE,)),
+                    StronglyConnectedComponentsVertexProgram: (L.RESULT_SCC,
+                                                               (StronglyConnectedComponentsVertexProgram.COMPONENT,))}
 
     def _result_mode(self):
         """resultMode if set, else the program's preferred (ResultGraph, Persist) as Fulgora
@@ -836,6 +877,11 @@ class GpuGraphComputer(TitanGraphComputer):
             eng = self.graph.engine_for(L.SCOPE_BOTH_E)
             props[KCoreVertexProgram.CORE], info = eng.kcore()
             iteration = info["levels"]
+            ids = eng.vertex_ids()
+        elif isinstance(p, StronglyConnectedComponentsVertexProgram):
+            eng = self.graph.engine_for(L.SCOPE_BOTH_E)
+            props[StronglyConnectedComponentsVertexProgram.COMPONENT], info = eng.scc()
+            iteration = info["rounds"]
             ids = eng.vertex_ids()
         else:
             raise TitanException(L.TGO_E_UNSUPPORTED, f"vertex program {type(p).__name__} is not supported on the GPU path")

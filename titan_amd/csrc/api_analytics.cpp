@@ -1,4 +1,5 @@
-// api_analytics.cpp — the analytics of a bothE load: connected components, triangles, k-core.
+// api_analytics.cpp — the analytics of a bothE load: connected components, triangles, k-core,
+// strongly connected components.
 #include "ctx.hpp"
 
 using namespace tgo;
@@ -31,6 +32,21 @@ static int cc_compress(tgo_ctx* ctx, int32_t& rounds) {
     }
 }
 
+// g.cc_tid = the Titan id of every internal index: once per graph (tgo_components and tgo_scc label with it).
+static int titan_ids_by_index(tgo_ctx* ctx) {
+    DevGraph& g = ctx->g;
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    const int64_t n = g.n;
+    if (g.cc_tid) return TGO_OK;
+    HIP_TRY(dev_alloc(ctx, g.cc_tid, n));
+    ctx->st.device_bytes = ctx->dev_bytes;
+    HIP_TRY(hipMemcpyAsync(s.msg, ctx->titan_id.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(k_cc_scatter_ids(s.msg, g.perm, g.cc_tid, n, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return TGO_OK;
+}
+
 int tgo_components(tgo_ctx* ctx, const tgo_cc_args* a, int64_t* label_out, tgo_cc_info* info) {
     int rc = bothE_program_check(ctx, a, "tgo_cc_args", "connected components run", nullptr);
     if (rc) return rc;
@@ -39,13 +55,7 @@ int tgo_components(tgo_ctx* ctx, const tgo_cc_args* a, int64_t* label_out, tgo_c
     hipStream_t st = ctx->stream;
     const int64_t n = g.n;
     int64_t* const label = s.dist;
-    if (!g.cc_tid) {                // Titan id of every internal index: once per graph
-        HIP_TRY(dev_alloc(ctx, g.cc_tid, n));
-        ctx->st.device_bytes = ctx->dev_bytes;
-        HIP_TRY(hipMemcpyAsync(s.msg, ctx->titan_id.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(k_cc_scatter_ids(s.msg, g.perm, g.cc_tid, n, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
+    if ((rc = titan_ids_by_index(ctx))) return rc;
     HIP_TRY(hipEventRecord(ctx->ev0, st));
     int32_t rounds = 0;
     const int path = g.has_transpose ? TGO_CC_PROPAGATE : TGO_CC_HOOK;
@@ -381,6 +391,238 @@ int tgo_copy_cores(tgo_ctx* ctx, int64_t* core_out) {
     (void)hipSetDevice(ctx->opts.device);
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return rows_out(ctx, ctx->sc.dist, core_out);
+}
+
+// ------------------------------------------------------------------ strongly connected components
+// SCC (scc.hip).  Nothing is cached with the graph but the Titan ids it shares with tgo_components.
+// Per run: comp (int32; -1 = live, else the representative) = sc.level, the live in- and
+// out-degrees = the halves of sc.vec[0] (as int32; the first half ends as the components' sizes),
+// colour and mark = the halves of sc.vec[1], the walks' queues = sc.q[0] / sc.q[1], the live lists
+// = sc.qdeg / sc.qpre (as int32), a live vertex's place in its list = sc.vec[2] (as int32), which
+// ends as the per-representative minimum (as int64), labels in internal order = sc.dist, row-order
+// staging = sc.msg.  Level control: Counters through publish_turn / wait_publish.
+// Defaults of TGO_TUNE_SCC_WAVE_ROW / _TAIL.
+constexpr int64_t kSccWaveRow = 64, kSccTailDefault = kSccTail;
+enum : int { kSccTrimWalk = 0, kSccForward = 1, kSccBackward = 2, kSccColourBack = 3 };
+
+struct SccRun {
+    SccGraph G;
+    SccState S;
+    int64_t n, wave_row;
+    bool trim;
+    int32_t* queue[2];
+    int64_t live;           // vertices without a component yet
+    int32_t rounds = 0;
+};
+
+// One publish of the level counters, which are zero again afterwards.
+static int scc_turn(tgo_ctx* ctx) {
+    Scratch& s = ctx->sc;
+    const unsigned long long seq = ++s.pub_seq;
+    HIP_TRY(k_publish_turn(s.cnt, s.hcnt_dev, seq, nullptr, ctx->stream));
+    int rc = wait_publish(ctx, seq);
+    if (rc) return rc;
+    if (s.hcnt->err) return fail(ctx, TGO_E_HIP, "strongly connected components: a queue overflowed (inconsistent lists)");
+    return TGO_OK;
+}
+
+// Walks queue[0][0, qlen) and whatever the walks discover, launch after launch, until a launch leaves
+// nothing queued.  A vertex is discovered at most once per walk: the loop ends within n discoveries.
+static int scc_walk_all(tgo_ctx* ctx, SccRun& r, int mode, int64_t qlen, int64_t& found) {
+    Scratch& s = ctx->sc;
+    found = 0;
+    for (int cur = 0; qlen > 0; cur ^= 1) {
+        HIP_TRY(k_scc_walk(mode, r.queue[cur], qlen, r.G, r.S, r.wave_row, r.queue[cur ^ 1], r.n, s.cnt, ctx->stream));
+        if (int rc = scc_turn(ctx)) return rc;
+        ++r.rounds;
+        const int64_t got = static_cast<int64_t>(s.hcnt->mf);
+        qlen = static_cast<int64_t>(s.hcnt->qlen);
+        found += got;
+        if (qlen > got || found > r.n)
+            return fail(ctx, TGO_E_HIP, "strongly connected components: inconsistent discovery count");
+    }
+    return TGO_OK;
+}
+
+// The trim walk of the qlen retired vertices in queue[0] and of every vertex it retires in turn.
+static int scc_trim(tgo_ctx* ctx, SccRun& r, int64_t qlen) {
+    if (!r.trim || qlen == 0) return TGO_OK;
+    DevSpan span(ctx->stream, "scc.trim", {"queued", qlen}, {"live", r.live});
+    int64_t found = 0;
+    if (int rc = scc_walk_all(ctx, r, kSccTrimWalk, qlen, found)) return rc;
+    if (found > r.live) return fail(ctx, TGO_E_HIP, "strongly connected components: inconsistent trim count");
+    r.live -= found;
+    return TGO_OK;
+}
+
+// The vertices of list (null: all) whose mark holds `bits` retire under rep (< 0: their colour), then the trim.
+static int scc_retire(tgo_ctx* ctx, SccRun& r, const int32_t* list, int64_t len, int32_t bits, int32_t rep) {
+    Scratch& s = ctx->sc;
+    HIP_TRY(k_scc_retire(list, len, r.S, bits, rep, r.trim ? r.queue[0] : nullptr, r.n, s.cnt, ctx->stream));
+    if (int rc = scc_turn(ctx)) return rc;
+    const int64_t got = static_cast<int64_t>(s.hcnt->mf), qlen = static_cast<int64_t>(s.hcnt->qlen);
+    if (got < 1 || got > r.live) return fail(ctx, TGO_E_HIP, "strongly connected components: no progress (a pass retired no vertex)");
+    r.live -= got;
+    return scc_trim(ctx, r, qlen);
+}
+
+// Forward-backward from the live vertex with the largest din * dout (the smallest id among equals).
+static int scc_pivot(tgo_ctx* ctx, SccRun& r) {
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    HIP_TRY(k_scc_pivot_pick(r.S, r.n, 0, 0, s.cnt, st));
+    int rc = scc_turn(ctx);
+    if (rc) return rc;
+    const unsigned long long product = s.hcnt->red[0];
+    if (!product) return fail(ctx, TGO_E_HIP, "strongly connected components: live vertices without a pivot");
+    HIP_TRY(k_scc_pivot_pick(r.S, r.n, 1, product, s.cnt, st));
+    if ((rc = scc_turn(ctx))) return rc;
+    const int64_t pivot = static_cast<int64_t>(0xFFFFFFFFULL - s.hcnt->red[0]);
+    if (pivot < 0 || pivot >= r.n) return fail(ctx, TGO_E_HIP, "strongly connected components: inconsistent pivot");
+    HIP_TRY(k_fill_i32(r.S.mark, 0, r.n, st));
+    int64_t found = 0;
+    {
+        DevSpan span(st, "scc.pivot_forward", {"pivot", pivot}, {"live", r.live});
+        HIP_TRY(k_scc_seed(r.S, static_cast<int32_t>(pivot), 3, r.queue[0], st));
+        if ((rc = scc_walk_all(ctx, r, kSccForward, 1, found))) return rc;
+    }
+    {
+        DevSpan span(st, "scc.pivot_backward", {"pivot", pivot}, {"forward", found + 1});
+        HIP_TRY(k_scc_seed(r.S, static_cast<int32_t>(pivot), 3, r.queue[0], st));
+        if ((rc = scc_walk_all(ctx, r, kSccBackward, 1, found))) return rc;
+    }
+    return scc_retire(ctx, r, nullptr, r.n, 3, static_cast<int32_t>(pivot));
+}
+
+// Colouring passes (on the grid, or all that remain in one workgroup) until no vertex is live.
+static int scc_colour_passes(tgo_ctx* ctx, SccRun& r, int64_t tail, int32_t& passes) {
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    int32_t* const lists[2] = {reinterpret_cast<int32_t*>(s.qdeg), reinterpret_cast<int32_t*>(s.qpre)};
+    int32_t* const pos = reinterpret_cast<int32_t*>(s.vec[2]);
+    const int32_t* list = nullptr;      // the live list in use (null: every vertex)
+    int64_t len = r.n;
+    int spare = 0, rc = TGO_OK;
+    while (r.live > 0) {
+        HIP_TRY(k_scc_live_list(list, len, r.S, lists[spare], pos, r.n, s.cnt, st));
+        if ((rc = scc_turn(ctx))) return rc;
+        list = lists[spare];
+        spare ^= 1;
+        len = static_cast<int64_t>(s.hcnt->qlen);
+        if (len != r.live) return fail(ctx, TGO_E_HIP, "strongly connected components: inconsistent live count");
+        if (tail > 0 && r.live <= tail) {
+            DevSpan span(st, "scc.tail", {"live", r.live});
+            HIP_TRY(k_scc_tail(list, len, r.G, r.S.comp, pos, r.trim, r.wave_row, s.cnt, st));
+            if ((rc = scc_turn(ctx))) return rc;
+            ++r.rounds;
+            passes += static_cast<int32_t>(s.hcnt->qlen);
+            if (static_cast<int64_t>(s.hcnt->mf) != r.live)
+                return fail(ctx, TGO_E_HIP, "strongly connected components: the tail left vertices without a component");
+            r.live = 0;
+            return TGO_OK;
+        }
+        ++passes;
+        {
+            DevSpan span(st, "scc.colour", {"pass", passes}, {"live", r.live});
+            HIP_TRY(k_scc_colour_init(list, len, r.S, st));
+            // a colour travels at least one arc per launch and no simple path has more than live - 1
+            for (int64_t launches = 1;; ++launches) {
+                HIP_TRY(k_scc_colour_round(list, len, r.G, r.S, r.wave_row, s.cnt, st));
+                if ((rc = scc_turn(ctx))) return rc;
+                ++r.rounds;
+                if (!s.hcnt->qlen) break;
+                if (launches > r.live)
+                    return fail(ctx, TGO_E_HIP, "strongly connected components: no progress (the colours do not settle)");
+            }
+        }
+        {
+            DevSpan span(st, "scc.colour_backward", {"pass", passes});
+            HIP_TRY(k_scc_roots(list, len, r.S, r.queue[0], r.n, s.cnt, st));
+            if ((rc = scc_turn(ctx))) return rc;
+            const int64_t roots = static_cast<int64_t>(s.hcnt->qlen);
+            if (roots < 1 || roots > r.live)
+                return fail(ctx, TGO_E_HIP, "strongly connected components: no progress (a pass without a root)");
+            int64_t found = 0;
+            if ((rc = scc_walk_all(ctx, r, kSccColourBack, roots, found))) return rc;
+        }
+        if ((rc = scc_retire(ctx, r, list, len, 1, -1))) return rc;
+    }
+    return TGO_OK;
+}
+
+int tgo_scc(tgo_ctx* ctx, const tgo_scc_args* a, int64_t* label_out, tgo_scc_info* info) {
+    int rc = bothE_program_check(ctx, a, "tgo_scc_args", "strongly connected components are computed",
+                                 "strongly connected components");
+    if (rc) return rc;
+    DevGraph& g = ctx->g;
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    const int64_t n = g.n;
+    int64_t* const label = s.dist;
+    if ((rc = titan_ids_by_index(ctx))) return rc;
+    HIP_TRY(hipEventRecord(ctx->ev0, st));
+    tgo_scc_info out{n, std::min<int64_t>(n, 1), n, 0, 0};
+    if (n == 0 || g.out.nnz + g.in.nnz == 0) {
+        // no arc: every vertex is its own component and nothing is launched for it
+        if (n > 0) HIP_TRY(hipMemcpyAsync(label, g.cc_tid, n * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        if ((rc = program_end(ctx, 0))) return rc;
+    } else {
+        SccRun r{};
+        int32_t* const half0 = reinterpret_cast<int32_t*>(s.vec[0]);
+        int32_t* const half1 = reinterpret_cast<int32_t*>(s.vec[1]);
+        r.G = SccGraph{g.out.off, g.out.adj, g.in.off, g.in.adj};
+        r.S = SccState{s.level, half0, half0 + n, half1, half1 + n};
+        r.n = n;
+        r.wave_row = tuned(ctx->scc_wave_row, kSccWaveRow);
+        r.trim = ctx->scc_trim != 0;
+        r.queue[0] = s.q[0];
+        r.queue[1] = s.q[1];
+        r.live = n;
+        const int64_t tail = std::min<int64_t>(tuned(ctx->scc_tail, kSccTailDefault), kSccTail);
+        HIP_TRY(k_level_prep(s.cnt, nullptr, 0, nullptr, st));
+        {
+            DevSpan span(st, "scc.trim", {"live", n});
+            HIP_TRY(k_scc_init(r.G, n, r.S, r.trim, r.wave_row, r.queue[0], s.cnt, st));
+            if ((rc = scc_turn(ctx))) return rc;
+            ++r.rounds;
+        }
+        const int64_t first = static_cast<int64_t>(s.hcnt->qlen);
+        if (first > n) return fail(ctx, TGO_E_HIP, "strongly connected components: inconsistent trim count");
+        r.live -= first;
+        if ((rc = scc_trim(ctx, r, first))) return rc;
+        if (ctx->scc_pivot != 0 && r.live > tail && (rc = scc_pivot(ctx, r))) return rc;
+        if ((rc = scc_colour_passes(ctx, r, tail, out.passes))) return rc;
+        // labels, and the device's own count of the vertices that have a component
+        int64_t* const minid = reinterpret_cast<int64_t*>(s.vec[2]);
+        int32_t* const size = r.S.din;
+        {
+            DevSpan span(st, "scc.label");
+            HIP_TRY(k_fill_i64(minid, INT64_MAX, n, st));
+            HIP_TRY(k_fill_i32(size, 0, n, st));
+            HIP_TRY(k_scc_fold(r.S.comp, g.cc_tid, n, minid, size, st));
+            HIP_TRY(k_scc_label(r.S.comp, minid, size, n, label, s.cnt, st));
+        }
+        if ((rc = scc_turn(ctx))) return rc;
+        out.components = static_cast<int64_t>(s.hcnt->qlen);
+        out.singletons = static_cast<int64_t>(s.hcnt->mf);
+        out.largest = static_cast<int64_t>(s.hcnt->red[0]);
+        out.rounds = r.rounds;
+        const int64_t retired = static_cast<int64_t>(s.hcnt->red[1]);
+        if ((rc = program_end(ctx, r.rounds))) return rc;
+        if (retired != n) return fail(ctx, TGO_E_HIP, "strongly connected components: vertices were left without a component");
+    }
+    if (info) *info = out;
+    if (label_out && (rc = rows_out(ctx, label, label_out))) return rc;
+    publish_result(ctx, TGO_RESULT_SCC, ResultSource{label, nullptr});
+    return TGO_OK;
+}
+
+int tgo_copy_scc(tgo_ctx* ctx, int64_t* label_out) {
+    if (!ctx || !label_out) return TGO_E_INVALID;
+    if (int rc = last_result_check(ctx, TGO_RESULT_SCC, "tgo_scc")) return rc;
+    (void)hipSetDevice(ctx->opts.device);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return rows_out(ctx, ctx->sc.dist, label_out);
 }
 
 }  // extern "C"

@@ -88,6 +88,10 @@ struct tgo_ctx {
     int64_t core_tail = -1;     // tgo_set_tuning(TGO_TUNE_CORE_TAIL): alive vertices one workgroup finishes; 0 = never
     int64_t core_lds_queue = -1;    // tgo_set_tuning(TGO_TUNE_CORE_LDS_QUEUE): entries of a workgroup's own queue
                                 // (< 0: the defaults kCoreWaveRow / kCoreTail / kCoreLdsQueue)
+    int64_t scc_wave_row = -1;  // tgo_set_tuning(TGO_TUNE_SCC_WAVE_ROW): row length from which a wave walks it
+    int64_t scc_tail = -1;      // tgo_set_tuning(TGO_TUNE_SCC_TAIL): live vertices one workgroup finishes; 0 = never
+    int scc_trim = -1;          // tgo_set_tuning(TGO_TUNE_SCC_TRIM / _PIVOT): 0 = the phase is skipped
+    int scc_pivot = -1;         // (< 0: the defaults kSccWaveRow / kSccTailDefault, both phases on)
     // state a native partitioned driver keeps between runs on this graph (part_driver.cpp:
     // the PageRank ghost lists); dropped with the graph
     std::shared_ptr<void> part_state;

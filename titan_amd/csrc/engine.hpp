@@ -958,6 +958,52 @@ hipError_t k_core_tail(const int32_t* list, int64_t len, const CoreView& g, int3
 hipError_t k_core_finish(const int32_t* deg, int64_t n, int32_t top, int64_t* core, unsigned long long* tot,
                          hipStream_t s);
 
+// Strongly connected components (scc.hip).  SccState over internal ids: comp = -1 while live, else
+// the representative; din / dout = live neighbours' entries other than self; colour / mark as the
+// phases use them.  k_scc_init: degrees, comp and (with trim) the first retired vertices to queue
+// (cnt->qlen).  k_scc_walk (mode 0 trim, 1 forward reach, 2 backward reach, 3 the colouring's
+// backward marks; one launch over cur): the discoveries its workgroups do not walk themselves to
+// next (cnt->qlen), cnt->mf += every discovery, cnt->err on a full queue.  k_scc_pivot_pick: step 0
+// cnt->red[0] = the largest din * dout + 1 over the live vertices, step 1 = UINT32_MAX - the
+// smallest id among those at `product`.  k_scc_retire: the live vertices of list (null: all) whose
+// mark holds `bits` get representative rep (< 0: their colour), cnt->mf of them, queued when queue
+// is given (cnt->qlen).  k_scc_live_list: keep / pos of the live vertices (cnt->qlen).
+// k_scc_colour_round: cnt->qlen += waves that raised a colour.  k_scc_roots: mark and queue the
+// vertices that kept their colour (cnt->qlen).  k_scc_tail (one workgroup, at most kSccTail live
+// vertices): cnt->qlen = passes, cnt->mf = retired, cnt->red[0] = sweeps.  k_scc_fold / k_scc_label:
+// minid (INT64_MAX before) and size (0 before) per representative, then the labels; cnt->qlen +=
+// components, cnt->mf += singletons, cnt->red[0] = the largest, cnt->red[1] += retired vertices.
+constexpr int kSccQueue = 256;      // entries of a workgroup's LDS queue buffer: what it follows itself
+constexpr int kSccTail = 4096;      // live vertices the one-workgroup tail holds in LDS
+struct SccGraph {
+    const int64_t* ooff; const int32_t* oadj;
+    const int64_t* ioff; const int32_t* iadj;
+};
+struct SccState {
+    int32_t *comp, *din, *dout, *colour, *mark;
+};
+hipError_t k_scc_init(const SccGraph& g, int64_t n, const SccState& st, bool trim, int64_t wave_row, int32_t* queue,
+                      Counters* cnt, hipStream_t s);
+hipError_t k_scc_walk(int mode, const int32_t* cur, int64_t qlen, const SccGraph& g, const SccState& st, int64_t wave_row,
+                      int32_t* next, int64_t n, Counters* cnt, hipStream_t s);
+hipError_t k_scc_pivot_pick(const SccState& st, int64_t n, int step, unsigned long long product, Counters* cnt,
+                            hipStream_t s);
+hipError_t k_scc_seed(const SccState& st, int32_t pivot, int32_t bits, int32_t* queue, hipStream_t s);
+hipError_t k_scc_retire(const int32_t* list, int64_t len, const SccState& st, int32_t bits, int32_t rep, int32_t* queue,
+                        int64_t n, Counters* cnt, hipStream_t s);
+hipError_t k_scc_live_list(const int32_t* list, int64_t len, const SccState& st, int32_t* keep, int32_t* pos, int64_t n,
+                           Counters* cnt, hipStream_t s);
+hipError_t k_scc_colour_init(const int32_t* list, int64_t len, const SccState& st, hipStream_t s);
+hipError_t k_scc_colour_round(const int32_t* list, int64_t len, const SccGraph& g, const SccState& st, int64_t wave_row,
+                              Counters* cnt, hipStream_t s);
+hipError_t k_scc_roots(const int32_t* list, int64_t len, const SccState& st, int32_t* queue, int64_t n, Counters* cnt,
+                       hipStream_t s);
+hipError_t k_scc_tail(const int32_t* list, int64_t len, const SccGraph& g, int32_t* comp, const int32_t* pos, bool trim,
+                      int64_t wave_row, Counters* cnt, hipStream_t s);
+hipError_t k_scc_fold(const int32_t* comp, const int64_t* tid, int64_t n, int64_t* minid, int32_t* size, hipStream_t s);
+hipError_t k_scc_label(const int32_t* comp, const int64_t* minid, const int32_t* size, int64_t n, int64_t* label,
+                       Counters* cnt, hipStream_t s);
+
 // PageRank gather diagnostics: [diag_lo, diag_hi) = only sources in this range are gathered
 // (the others read as 0; results invalid) — attributes the update's time to source ranges.
 struct PrTuning {

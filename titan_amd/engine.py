@@ -391,6 +391,26 @@ class Engine:
         _check(self.lib, self.ctx, self.lib.tgo_copy_cores(self.ctx, L.ptr(out, C.c_int64)))
         return out
 
+    def scc(self, fetch=True):
+        """Strongly connected components of a bothE load read as a directed graph (tgo_scc): an arc
+        u -> v for every OUT entry of u that names v.  (labels, info) — labels[v] = the smallest
+        Titan id among the vertices that v reaches and that reach v, in row order (None when fetch is
+        False: the labels stay on the device for copy_scc / result_rows); info = dict(components,
+        largest, singletons, rounds, passes).  rounds (device launches of the trim, reach and
+        colouring loops) and passes (colouring passes) are diagnostics and may differ run to run."""
+        a = L.SccArgs(L.SCOPE_BOTH_E, 0)
+        info = L.SccInfo()
+        out = np.zeros(self.n, dtype=np.int64) if fetch else None
+        _check(self.lib, self.ctx, self.lib.tgo_scc(self.ctx, C.byref(a), L.ptr(out, C.c_int64), C.byref(info)))
+        return out, {"components": int(info.components), "largest": int(info.largest),
+                     "singletons": int(info.singletons), "rounds": int(info.rounds), "passes": int(info.passes)}
+
+    def copy_scc(self):
+        """The labels of the last scc() run, in row order."""
+        out = np.zeros(self.n, dtype=np.int64)
+        _check(self.lib, self.ctx, self.lib.tgo_copy_scc(self.ctx, L.ptr(out, C.c_int64)))
+        return out
+
     def result_rows(self, kind, key_ids, datatypes, relation_id_base):
         """Edgestore entries of the last program's compute keys (tgo_result_rows): the rows
         ResultMode PERSIST writes back (FulgoraGraphComputer.java:248-305)."""
