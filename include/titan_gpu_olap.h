@@ -377,12 +377,17 @@ int  tgo_copy_multi_distances(tgo_ctx* ctx, int32_t source, int64_t* dist_out);
  * TGO_TUNE_SCC_TRIM / TGO_TUNE_SCC_PIVOT: 0 = the trim / the pivot's forward-backward reach is
  * skipped and the later phases do its work (for tests), 1 = it runs.  For all four < 0 = the
  * default, and every value gives the same labels. */
+/* TGO_TUNE_BC_WAVE_ROW (tgo_betweenness): a row of at least this many entries is summed by its whole
+ * wave (64 strided partial sums, then a fixed tree) instead of its own lane; an integer >= 1, < 0 =
+ * the default.  The two paths add a row's terms in different orders: results at different values
+ * agree within the rounding bound of the contract, not bit for bit; at one value they are
+ * bit-identical run to run. */
 enum { TGO_TUNE_MS_SPLIT = 1, TGO_TUNE_MS_GHOST = 2, TGO_TUNE_DS_BINS = 3, TGO_TUNE_DS_PILE_CAP = 4,
        TGO_TUNE_DS_DONE = 5, TGO_TUNE_MS_COLD = 6, TGO_TUNE_DS_PULL = 7, TGO_TUNE_DS_SMALL = 8,
        TGO_TUNE_MS_STAY = 9, TGO_TUNE_MS_SPARSE = 10, TGO_TUNE_TRI_WAVE_ROW = 11,
        TGO_TUNE_TRI_BLOCK_ROW = 12, TGO_TUNE_MS_HEAD = 13, TGO_TUNE_CORE_WAVE_ROW = 14,
        TGO_TUNE_CORE_TAIL = 15, TGO_TUNE_CORE_LDS_QUEUE = 16, TGO_TUNE_SCC_WAVE_ROW = 17,
-       TGO_TUNE_SCC_TAIL = 18, TGO_TUNE_SCC_TRIM = 19, TGO_TUNE_SCC_PIVOT = 20 };
+       TGO_TUNE_SCC_TAIL = 18, TGO_TUNE_SCC_TRIM = 19, TGO_TUNE_SCC_PIVOT = 20, TGO_TUNE_BC_WAVE_ROW = 21 };
 int  tgo_set_tuning(tgo_ctx* ctx, int32_t key, double value);
 
 /* ---- Tracing (the reference's only hook is FulgoraGraphComputer.java:143,307
@@ -507,6 +512,49 @@ typedef struct { int64_t components, largest, singletons; int32_t rounds, passes
 int  tgo_scc(tgo_ctx* ctx, const tgo_scc_args* args, int64_t* label_out, tgo_scc_info* info);
 int  tgo_copy_scc(tgo_ctx* ctx, int64_t* label_out);
 
+/* ---- Betweenness centrality ---------------------------------------------------------------
+ * Brandes' betweenness over a bothE load, read one of two ways:
+ *   directed = 0  the simple undirected projection of tgo_triangles / tgo_kcore: u ~ v iff u != v and
+ *                 an OUT or IN entry of u names v; parallel edges, the two directions of a pair and
+ *                 self-loops collapse
+ *   directed = 1  the directed graph of tgo_scc: an arc u -> v iff an OUT entry of u names v; parallel
+ *                 arcs and self-loops change nothing
+ * Either way a shortest path is a sequence of vertices (a parallel edge does not multiply path
+ * counts), and a vertex cut counts as its canonical vertex.  Per vertex in row order:
+ *   bc[v] = sum over the seeds s, in the order given, of delta_s(v),
+ *   delta_s(v) = sum over t not in {s, v} reachable from s of sigma_st(v) / sigma_st
+ * (sigma counts shortest s-t paths; endpoints are excluded).  This is the RAW sum over ordered pairs:
+ * it is not halved for the undirected reading and not normalised — the first is one exact
+ * multiplication by 0.5, the second one rounding multiplication, both left to the caller.
+ * seeds: nseeds Titan ids (args->seed_is_dense: row-order indices), resolved as tgo_bfs resolves its
+ * seed; nseeds = -1 with seeds = NULL: every executed vertex in row order (exact betweenness);
+ * nseeds = 0: all zeros.  A seed given twice counts twice; a seed that is no executed vertex
+ * contributes nothing and is not counted in info->sources.
+ * Arithmetic: sigma and delta are fp64; every sum is folded in an order fixed by the graph and the
+ * tuning values alone, so results are bit-identical run to run at fixed tuning values; across
+ * TGO_TUNE_BC_WAVE_ROW values, or against another summation order, they agree within
+ * (3 D (dmax + 3) + S) 2^-52 relative (D the deepest level, dmax the longest distinct-neighbour row,
+ * S the seeds).  Every term is non-negative: a vertex whose exact value is 0 gets exactly 0.0.  A
+ * sigma beyond the range of a double fails the call with TGO_E_PROGRAM (the message names the seed;
+ * detected by a flag set on the device); the ctx stays usable.  info:
+ *   sources        seeds run; also tgo_stats.iterations
+ *   reached_pairs  sum over the seeds s of the vertices reached from s, s excluded; deterministic
+ *   max_depth      the deepest BFS level seen; deterministic; also tgo_stats.levels
+ *   rounds         device launches of the two sweeps; a DIAGNOSTIC
+ * args->scope must be TGO_SCOPE_BOTH_E and the loaded scope, args->flags 0, args->directed 0 or 1,
+ * nseeds >= -1, seeds non-NULL when nseeds > 0 (else TGO_E_INVALID).  Lists that are not each other's
+ * transpose (tgo_load_csr with asymmetric rows) and a partitioned ctx: TGO_E_UNSUPPORTED.  A failed
+ * call leaves the ctx usable.  bc_out NULL: the result stays on the device (tgo_copy_betweenness;
+ * tgo_result_rows kind TGO_RESULT_BETWEENNESS).  tgo_copy_betweenness after another program:
+ * TGO_E_STATE.  The first directed = 0 run builds the simple adjacency (every vertex's sorted distinct
+ * neighbours other than itself: 4 bytes per entry + 8 (n + 1), tgo_stats.device_bytes) and keeps it
+ * with the graph. */
+typedef struct { int32_t scope; int32_t flags; int32_t directed; int32_t seed_is_dense; } tgo_bc_args;
+typedef struct { int64_t sources, reached_pairs; int32_t max_depth, rounds; } tgo_bc_info;
+int  tgo_betweenness(tgo_ctx* ctx, const tgo_bc_args* args, const int64_t* seeds, int64_t nseeds,
+                     double* bc_out, tgo_bc_info* info);
+int  tgo_copy_betweenness(tgo_ctx* ctx, double* bc_out);
+
 /* ---- Generic vertex programs ----------------------------------------
  * A vertex program the engine does not implement natively runs its execute() on the host
  * over whole per-vertex vectors (titan_amd/computer.py GenericVertexProgram; the Java host
@@ -616,6 +664,8 @@ int  tgo_dense_ids(tgo_ctx* ctx, const int64_t* titan_ids, int64_t count, int64_
  *   CORE      tgo_kcore's core number (Long, or Integer: a core number is at most d(v) < 2^31) on
  *             every executed vertex; any other typed key: TGO_E_INVALID
  *   SCC       tgo_scc's label, encoded exactly as COMPONENT
+ *   BETWEENNESS  tgo_betweenness's value (Double) on every executed vertex, encoded exactly as
+ *             PAGE_RANK; any other typed key: TGO_E_INVALID
  * Compute keys are typed property keys of those datatypes, or generic keys (TGO_DT_OBJECT: what
  * getOrCreatePropertyKey makes for a key the program sets without a schema, DefaultSchemaMaker
  * .java:46-48), whose values carry their class (Long 13, Double 20, Integer 12).  Relation ids are
@@ -625,11 +675,11 @@ int  tgo_dense_ids(tgo_ctx* ctx, const int64_t* titan_ids, int64_t count, int64_
  * (the tgo_rows layout, so the rows can be scanned again). */
 typedef enum { TGO_RESULT_DISTANCE = 0, TGO_RESULT_PAGERANK = 1, TGO_RESULT_DEGREE = 2,
                TGO_RESULT_VALUES = 3, TGO_RESULT_COMPONENT = 4, TGO_RESULT_TRIANGLES = 5,
-               TGO_RESULT_CORE = 6, TGO_RESULT_SCC = 7 } tgo_result_kind;
+               TGO_RESULT_CORE = 6, TGO_RESULT_SCC = 7, TGO_RESULT_BETWEENNESS = 8 } tgo_result_kind;
 typedef struct {
     int32_t kind;                 /* tgo_result_kind                                          */
     int32_t reserved;             /* TGO_RESULT_VALUES: tgo_value_type of the values           */
-    int64_t key_ids[2];           /* [0] DISTANCE / PAGE_RANK / DEGREE / COMPONENT / TRIANGLES / CORE / SCC key; [1] OUTGOING_EDGE_COUNT / CLUSTERING */
+    int64_t key_ids[2];           /* [0] DISTANCE / PAGE_RANK / DEGREE / COMPONENT / TRIANGLES / CORE / SCC / BETWEENNESS key; [1] OUTGOING_EDGE_COUNT / CLUSTERING */
     int32_t datatypes[2];         /* tgo_datatype of each key                                  */
     int64_t relation_id_base;
 } tgo_result_args;

@@ -331,6 +331,34 @@ JNIEXPORT jlongArray JNICALL JFN(scc)(JNIEnv* env, jclass cls, jlong h) {
     return distances(env, h, run_scc, &a);
 }
 
+/* tgo_betweenness over the bothE load (directed: its OUT entries as arcs, else the simple undirected
+ * projection): every vertex's raw betweenness in row order, summed over the seeds (Titan ids; a null
+ * array: every vertex), or NULL on error (the seeds run are tgo_stats.iterations afterwards;
+ * write-back: tgo_result_rows kind TGO_RESULT_BETWEENNESS). */
+JNIEXPORT jdoubleArray JNICALL JFN(betweenness)(JNIEnv* env, jclass cls, jlong h, jlongArray seeds, jboolean directed) {
+    (void)cls;
+    if (!fits_jsize(env, tgo_num_vertices(CTX(h)), "more vertices than a Java array holds")) return NULL;
+    jsize n = (jsize)tgo_num_vertices(CTX(h));
+    jdoubleArray out = (*env)->NewDoubleArray(env, n);
+    if (!out) return NULL;
+    tgo_bc_args a;
+    memset(&a, 0, sizeof a);
+    a.scope = TGO_SCOPE_BOTH_E;
+    a.directed = directed ? 1 : 0;
+    jlong* s = NULL;
+    int64_t nseeds = -1;
+    if (seeds) {
+        nseeds = (*env)->GetArrayLength(env, seeds);
+        s = (*env)->GetLongArrayElements(env, seeds, NULL);
+        if (!s) return NULL;
+    }
+    jdouble* p = (*env)->GetDoubleArrayElements(env, out, NULL);
+    int rc = p ? tgo_betweenness(CTX(h), &a, nseeds > 0 ? (const int64_t*)s : NULL, nseeds, (double*)p, NULL) : TGO_E_OOM;
+    if (p) (*env)->ReleaseDoubleArrayElements(env, out, p, 0);
+    if (s) (*env)->ReleaseLongArrayElements(env, seeds, s, JNI_ABORT);
+    return rc == TGO_OK ? out : NULL;
+}
+
 /* tgo_result_rows: Object[5] = {long[] rowKeys, long[] rowEntryBegin, long[] rowByteBegin,
  * long[] entryLimitValuePos, byte[] entryBytes}, or NULL on error (status: lastError; a result
  * beyond the int32 index range of a Java array: IllegalStateException). */

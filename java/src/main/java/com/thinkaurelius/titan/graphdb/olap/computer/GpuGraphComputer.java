@@ -47,7 +47,8 @@ import java.util.concurrent.Future;
  * (weakly connected components over bothE, tgo_components), a TriangleCountVertexProgram
  * (triangles and clustering coefficients of the simple undirected projection, tgo_triangles) and
  * a KCoreVertexProgram (core numbers of the same projection, tgo_kcore),
- * a StronglyConnectedComponentsVertexProgram (bothE read as a directed graph, tgo_scc).
+ * a StronglyConnectedComponentsVertexProgram (bothE read as a directed graph, tgo_scc),
+ * a BetweennessCentralityVertexProgram (Brandes' betweenness over either reading, tgo_betweenness).
  *
  * Write-back (FulgoraGraphComputer.java:248-305): with Persist.VERTEX_PROPERTIES the compute
  * keys are encoded on the device (tgo_result_rows: single-cardinality property entries, one
@@ -546,9 +547,20 @@ public class GpuGraphComputer implements TitanGraphComputer {
                     return new KCore();
                 case "com.thinkaurelius.titan.olap.StronglyConnectedComponentsVertexProgram":
                     return new StronglyConnectedComponents();
+                case "com.thinkaurelius.titan.olap.BetweennessCentralityVertexProgram":
+                    return new Betweenness(seedsOf(conf), conf.getBoolean("titan.betweenness.directed", false));
                 default:
                     throw new TitanException("vertex program " + p.getClass().getName() + " is not supported on the GPU path");
             }
+        }
+
+        /** titan.betweenness.seeds: the Titan ids the sum runs over, in order; absent: every vertex (null). */
+        private static long[] seedsOf(BaseConfiguration conf) {
+            if (!conf.containsKey("titan.betweenness.seeds")) return null;
+            java.util.List<?> l = conf.getList("titan.betweenness.seeds");
+            long[] s = new long[l.size()];
+            for (int i = 0; i < s.length; i++) s[i] = Long.parseLong(l.get(i).toString());
+            return s;
         }
 
         private static int lengthOf(VertexProgram<?> p) {
@@ -764,6 +776,33 @@ public class GpuGraphComputer implements TitanGraphComputer {
         }
         void emit(long[] ids, Map<String, Object> values, FulgoraMapEmitter emitter) {
             long[] c = (long[]) values.get(COMPONENT);
+            for (int i = 0; i < ids.length; i++) emitter.emit(ids[i], c[i]);
+        }
+    }
+
+    /**
+     * Brandes' betweenness centrality over bothE (tgo_betweenness): CENTRALITY = the sum over the
+     * seeds of their dependency on the vertex, the raw sum over ordered pairs (neither halved nor
+     * normalised).  The iteration reported is the number of seeds run, known after run().
+     */
+    static final class Betweenness extends DeviceProgram {
+        static final String CENTRALITY = "titan.betweenness.centrality";
+        final long[] seeds; final boolean directed;
+        private int sources;
+        Betweenness(long[] seeds, boolean directed) { this.seeds = seeds; this.directed = directed; }
+        int scope() { return TgoNative.SCOPE_BOTH_E; }
+        int iterations() { return sources; }
+        int resultKind() { return TgoNative.RESULT_BETWEENNESS; }
+        String[] computeKeys() { return new String[]{CENTRALITY}; }
+        int[] computeKeyTypes() { return new int[]{TgoNative.DT_DOUBLE}; }
+        Map<String, Object> run(long ctx) {
+            Map<String, Object> v = new HashMap<>();
+            v.put(CENTRALITY, TgoNative.checked(ctx, TgoNative.betweenness(ctx, seeds, directed)));
+            sources = (int) TgoNative.stats(ctx)[3];
+            return v;
+        }
+        void emit(long[] ids, Map<String, Object> values, FulgoraMapEmitter emitter) {
+            double[] c = (double[]) values.get(CENTRALITY);
             for (int i = 0; i < ids.length; i++) emitter.emit(ids[i], c[i]);
         }
     }

@@ -102,12 +102,20 @@ public final class TgoNative {
      */
     public static native long[] scc(long ctx);
 
+    /**
+     * tgo_betweenness over a bothE load: every vertex's raw betweenness (the sum over ordered pairs,
+     * neither halved nor normalised) in row order, summed over the seeds (Titan ids, in that order;
+     * null: every vertex); directed: the OUT entries as arcs, else the simple undirected projection.
+     * null on failure.  stats()[3] then holds the seeds run.
+     */
+    public static native double[] betweenness(long ctx, long[] seeds, boolean directed);
+
     /** tgo_stats_get: {ghostVertices, truncatedResults, skippedRows, iterations, loadMs, lastKernelMs}. */
     public static native double[] stats(long ctx);
 
     /** tgo_result_kind */
     public static final int RESULT_DISTANCE = 0, RESULT_PAGERANK = 1, RESULT_DEGREE = 2, RESULT_COMPONENT = 4,
-            RESULT_TRIANGLES = 5, RESULT_CORE = 6, RESULT_SCC = 7;
+            RESULT_TRIANGLES = 5, RESULT_CORE = 6, RESULT_SCC = 7, RESULT_BETWEENNESS = 8;
     /**
      * tgo_result_rows: the edgestore entries (single-cardinality property entries) of the last
      * program's compute keys, as {long[] rowKeys, long[] rowEntryBegin, long[] rowByteBegin,

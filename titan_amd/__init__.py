@@ -6,6 +6,7 @@ TitanGraphComputer API plus a thin ctypes binding; it has no CPU fallback.
 """
 from .engine import Engine, Rows, Schema, TitanException, rmat_edges, pick_roots, synth_rows  # noqa: F401
 from .computer import (  # noqa: F401
+    BetweennessCentralityVertexProgram, BetweennessRankMapReduce,
     ClusterCountMapReduce, ClusterPopulationMapReduce, ConnectedComponentVertexProgram, CoreSizeMapReduce,
     DegeneracyMapReduce, DegreeCounter, DegreeMapper, ExecutionException, GpuGraph, GpuGraphComputer,
     KCoreVertexProgram, KeyValue,
@@ -29,4 +30,5 @@ __all__ = [
     "TriangleCountVertexProgram", "TriangleCountMapReduce", "TransitivityMapReduce",
     "KCoreVertexProgram", "DegeneracyMapReduce", "CoreSizeMapReduce",
     "StronglyConnectedComponentsVertexProgram", "SccSizeMapReduce",
+    "BetweennessCentralityVertexProgram", "BetweennessRankMapReduce",
 ]

@@ -35,6 +35,7 @@ RESULT_COMPONENT = 4
 RESULT_TRIANGLES = 5
 RESULT_CORE = 6
 RESULT_SCC = 7
+RESULT_BETWEENNESS = 8
 CC_HOOK, CC_PROPAGATE = 0, 1     # tgo_cc_path
 SSSP_HOP_BOUNDED, SSSP_DELTA = 0, 1
 FLAG_STATS = 1
@@ -47,6 +48,8 @@ TUNE_TRI_WAVE_ROW, TUNE_TRI_BLOCK_ROW = 11, 12   # tgo_triangles: forward-row le
 TUNE_CORE_WAVE_ROW, TUNE_CORE_TAIL, TUNE_CORE_LDS_QUEUE = 14, 15, 16
 # tgo_scc: row length of the wave path, live vertices one workgroup finishes, trim / pivot phase on (1) or skipped (0)
 TUNE_SCC_WAVE_ROW, TUNE_SCC_TAIL, TUNE_SCC_TRIM, TUNE_SCC_PIVOT = 17, 18, 19, 20
+# tgo_betweenness: row length from which a wave sums a row (results across values agree within rounding, not bit for bit)
+TUNE_BC_WAVE_ROW = 21
 TRACE_JSON, TRACE_ROCTX = 1, 2   # tgo_trace_enable flags
 DIST_ABSENT = -(1 << 63)
 ABI_VERSION = 2
@@ -173,6 +176,14 @@ class SccInfo(C.Structure):
                 ("rounds", C.c_int32), ("passes", C.c_int32)]
 
 
+class BcArgs(C.Structure):
+    _fields_ = [("scope", C.c_int32), ("flags", C.c_int32), ("directed", C.c_int32), ("seed_is_dense", C.c_int32)]
+
+
+class BcInfo(C.Structure):
+    _fields_ = [("sources", C.c_int64), ("reached_pairs", C.c_int64), ("max_depth", C.c_int32), ("rounds", C.c_int32)]
+
+
 class GatherArgs(C.Structure):
     _fields_ = [("scope", C.c_int32), ("value_type", C.c_int32), ("combiner", C.c_int32), ("edge_fn", C.c_int32)]
 
@@ -202,7 +213,7 @@ EXPORTS = [
     "tgo_gather", "tgo_combine_global", "tgo_dense_ids", "tgo_decode_edge_entry", "tgo_result_rows",
     "tgo_gather_lists", "tgo_result_rows_values", "tgo_set_edge_program",
     "tgo_components", "tgo_copy_components", "tgo_triangles", "tgo_copy_triangles",
-    "tgo_kcore", "tgo_copy_cores", "tgo_scc", "tgo_copy_scc",
+    "tgo_kcore", "tgo_copy_cores", "tgo_scc", "tgo_copy_scc", "tgo_betweenness", "tgo_copy_betweenness",
     "tgo_rmat_edges", "tgo_rmat_edges_device", "tgo_rmat_partition_device", "tgo_pick_roots", "tgo_synth_rows",
     # titan_gpu_olap_part.h (1-D vertex-partitioned multi-GPU)
     "tgo_load_partition", "tgo_part_layout", "tgo_load_partition_layout", "tgo_part_bfs_begin", "tgo_part_bfs_td", "tgo_part_bfs_claim", "tgo_part_bfs_bu",
@@ -267,6 +278,8 @@ def load() -> C.CDLL:
         "tgo_copy_cores": (C.c_int, [vp, _i64p]),
         "tgo_scc": (C.c_int, [vp, P(SccArgs), _i64p, P(SccInfo)]),
         "tgo_copy_scc": (C.c_int, [vp, _i64p]),
+        "tgo_betweenness": (C.c_int, [vp, P(BcArgs), _i64p, C.c_int64, C.POINTER(C.c_double), P(BcInfo)]),
+        "tgo_copy_betweenness": (C.c_int, [vp, C.POINTER(C.c_double)]),
         "tgo_pagerank": (C.c_int, [vp, P(PrArgs), C.POINTER(C.c_double)]),
         "tgo_walkcount": (C.c_int, [vp, C.c_int32, _i32p]),
         "tgo_stats_get": (C.c_int, [vp, P(Stats)]),

@@ -441,6 +441,42 @@ class StronglyConnectedComponentsVertexProgram(VertexProgram):
         return StronglyConnectedComponentsVertexProgram.Builder()
 
 
+class BetweennessCentralityVertexProgram(VertexProgram):
+    """Brandes' betweenness centrality over bothE (tgo_betweenness): the simple undirected projection,
+    or with directed(True) the directed graph of the OUT edges.  CENTRALITY = the sum over the seeds
+    s of the dependency of s on the vertex (Double): the raw sum over ordered pairs, neither halved
+    nor normalised.  seeds(ids): the Titan ids the sum runs over, in that order; without it every
+    vertex (exact betweenness).  memory.getIteration() reports the seeds run.  Result graph and
+    persist preference as ShortestDistanceVertexProgram."""
+    CENTRALITY = "titan.betweenness.centrality"
+    compute_keys = (CENTRALITY,)
+    scope_name = "bothE"
+
+    def __init__(self, seeds=None, directed=False):
+        self.seeds = None if seeds is None else [int(s) for s in seeds]
+        self.directed = bool(directed)
+
+    class Builder:
+        def __init__(self):
+            self._seeds = None
+            self._directed = False
+
+        def seeds(self, ids):
+            self._seeds = [int(s) for s in ids]
+            return self
+
+        def directed(self, on=True):
+            self._directed = bool(on)
+            return self
+
+        def create(self, graph=None):
+            return BetweennessCentralityVertexProgram(self._seeds, self._directed)
+
+    @staticmethod
+    def build():
+        return BetweennessCentralityVertexProgram.Builder()
+
+
 # ----------------------------------------------------------------------------- map-reduces
 class MapReduce:
     memory_key = ""
@@ -643,6 +679,45 @@ class SccSizeMapReduce(MapReduce):
         return {int(k): int(v) for k, v in zip(u, c)}
 
 
+class BetweennessRankMapReduce(MapReduce):
+    """The `top` vertices of largest betweenness as (Titan id, value) pairs, largest first, ties
+    broken by the smaller id."""
+    DEFAULT_MEMORY_KEY = "betweennessRank"
+
+    def __init__(self, key=DEFAULT_MEMORY_KEY, top=10):
+        self.memory_key = key
+        self.top = int(top)
+
+    class Builder:
+        def __init__(self):
+            self._k = BetweennessRankMapReduce.DEFAULT_MEMORY_KEY
+            self._top = 10
+
+        def memoryKey(self, k):  # noqa: N802
+            self._k = k
+            return self
+
+        def top(self, k):
+            self._top = int(k)
+            return self
+
+        def create(self):
+            return BetweennessRankMapReduce(self._k, self._top)
+
+    @staticmethod
+    def build():
+        return BetweennessRankMapReduce.Builder()
+
+    def emit(self, ids, props):
+        bc = props.get(BetweennessCentralityVertexProgram.CENTRALITY)
+        if bc is None:
+            return []
+        ids = np.asarray(ids, dtype=np.int64)
+        bc = np.asarray(bc, dtype=np.float64)
+        order = np.lexsort((ids, -bc))[:max(self.top, 0)]
+        return [KeyValue(int(ids[i]), float(bc[i])) for i in order]
+
+
 class DegreeMapper(MapReduce):
     DEGREE_RESULT = "degrees"                 # OLAPTest.java:420
     memory_key = DEGREE_RESULT
@@ -770,7 +845,9 @@ class GpuGraphComputer(TitanGraphComputer):
                                                                       TriangleCountVertexProgram.CLUSTERING)),
                     KCoreVertexProgram: (L.RESULT_CORE, (KCoreVertexProgram.CORE,)),
                     StronglyConnectedComponentsVertexProgram: (L.RESULT_SCC,
-                                                               (StronglyConnectedComponentsVertexProgram.COMPONENT,))}
+                                                               (StronglyConnectedComponentsVertexProgram.COMPONENT,)),
+                    BetweennessCentralityVertexProgram: (L.RESULT_BETWEENNESS,
+                                                         (BetweennessCentralityVertexProgram.CENTRALITY,))}
 
     def _result_mode(self):
         """resultMode if set, else the program's preferred (ResultGraph, Persist) as Fulgora
@@ -882,6 +959,11 @@ class GpuGraphComputer(TitanGraphComputer):
             eng = self.graph.engine_for(L.SCOPE_BOTH_E)
             props[StronglyConnectedComponentsVertexProgram.COMPONENT], info = eng.scc()
             iteration = info["rounds"]
+            ids = eng.vertex_ids()
+        elif isinstance(p, BetweennessCentralityVertexProgram):
+            eng = self.graph.engine_for(L.SCOPE_BOTH_E)
+            props[BetweennessCentralityVertexProgram.CENTRALITY], info = eng.betweenness(p.seeds, directed=p.directed)
+            iteration = info["sources"]
             ids = eng.vertex_ids()
         else:
             raise TitanException(L.TGO_E_UNSUPPORTED, f"vertex program {type(p).__name__} is not supported on the GPU path")

@@ -198,6 +198,11 @@ int tgo_set_tuning(tgo_ctx* ctx, int32_t key, double value) {
             return fail(ctx, TGO_E_INVALID, "TGO_TUNE_SCC_TRIM / _PIVOT: 0 (the phase is skipped) or 1 (< 0: the default)");
         (key == TGO_TUNE_SCC_TRIM ? ctx->scc_trim : ctx->scc_pivot) = value < 0.0 ? -1 : static_cast<int>(value);
         return TGO_OK;
+    case TGO_TUNE_BC_WAVE_ROW:
+        if (!(value < 0.0) && !(value >= 1.0 && value <= 9.0e15 && value == static_cast<double>(static_cast<int64_t>(value))))
+            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_BC_WAVE_ROW: a row length >= 1 (< 0: the default)");
+        ctx->bc_wave_row = value < 0.0 ? -1 : static_cast<int64_t>(value);
+        return TGO_OK;
     default:
         return fail(ctx, TGO_E_INVALID, "tgo_set_tuning: unknown key");
     }

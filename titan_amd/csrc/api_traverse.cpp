@@ -7,7 +7,7 @@
 
 using namespace tgo;
 
-namespace {
+namespace tgo {
 
 // Direction-optimizing level loop for unit weights (Beamer et al., SC'12 heuristics).
 int run_bfs(tgo_ctx* ctx, int64_t seed, int max_depth, int scope) {
@@ -92,6 +92,10 @@ int run_bfs(tgo_ctx* ctx, int64_t seed, int max_depth, int scope) {
     ctx->st.iterations = max_depth;   // the reference always runs iterations 0..maxDepth
     return TGO_OK;
 }
+
+}  // namespace tgo
+
+namespace {
 
 int run_sssp(tgo_ctx* ctx, int64_t seed, int max_depth, int scope, bool weighted) {
     DevGraph& g = ctx->g;

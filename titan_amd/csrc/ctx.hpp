@@ -92,6 +92,8 @@ struct tgo_ctx {
     int64_t scc_tail = -1;      // tgo_set_tuning(TGO_TUNE_SCC_TAIL): live vertices one workgroup finishes; 0 = never
     int scc_trim = -1;          // tgo_set_tuning(TGO_TUNE_SCC_TRIM / _PIVOT): 0 = the phase is skipped
     int scc_pivot = -1;         // (< 0: the defaults kSccWaveRow / kSccTailDefault, both phases on)
+    int64_t bc_wave_row = -1;   // tgo_set_tuning(TGO_TUNE_BC_WAVE_ROW): row length from which a wave sums it
+                                // (< 0: the default kBcWaveRow)
     // state a native partitioned driver keeps between runs on this graph (part_driver.cpp:
     // the PageRank ghost lists); dropped with the graph
     std::shared_ptr<void> part_state;
@@ -285,6 +287,10 @@ int fx_take_bad(tgo_ctx* ctx, ColdBlocks& cb, bool* bad);
 
 // ------------------------------------------------------------------ api_traverse.cpp
 int64_t default_delta(const DevGraph& g, bool weighted);
+// The direction-optimizing BFS from internal vertex `seed` (< 0: nobody is reached) along `scope`'s
+// lists: levels in sc.level (-1 unreached), distances in sc.dist, tgo_stats.levels = levels run
+// (the deepest level + 1).  tgo_bfs and tgo_betweenness (api_analytics.cpp) run it.
+int run_bfs(tgo_ctx* ctx, int64_t seed, int max_depth, int scope);
 
 // ------------------------------------------------------------------ api_msbfs.cpp
 int ms_alloc(tgo_ctx* ctx);

@@ -481,6 +481,11 @@ struct DevGraph {
     int64_t* core_boff = nullptr;   // n + 1
     int32_t* core_badj = nullptr;   // tri_fnnz
     unsigned long long* core_tot = nullptr;  // 2 words per run: vertices of the innermost core, max core
+    // simple adjacency (tgo_betweenness with directed = 0, built on its first such run): adj(v) = the
+    // sorted distinct neighbours other than v, internal ids
+    int64_t* bc_soff = nullptr;     // n + 1
+    int32_t* bc_sadj = nullptr;     // bc_snnz
+    int64_t bc_snnz = 0, bc_smax = 0;   // its entries and its longest row
 };
 
 // Views of the loaded scope.
@@ -1003,6 +1008,30 @@ hipError_t k_scc_tail(const int32_t* list, int64_t len, const SccGraph& g, int32
 hipError_t k_scc_fold(const int32_t* comp, const int64_t* tid, int64_t n, int64_t* minid, int32_t* size, hipStream_t s);
 hipError_t k_scc_label(const int32_t* comp, const int64_t* minid, const int32_t* size, int64_t n, int64_t* label,
                        Counters* cnt, hipStream_t s);
+
+// Betweenness centrality (bc.hip).  k_bc_adj_count / _fill: the simple adjacency's row lengths
+// (cnt[n] = 0 for the scan) and, into the scanned offsets, its entries.  k_bc_level_count: hist[l]
+// += the vertices of level l in [0, depth] (zero before; a deeper level raises cnt->err);
+// k_bc_level_scatter: order = those vertices by level, cursor = the levels' offsets before (a slot
+// past n raises cnt->err).  k_bc_sigma / k_bc_delta: one level's slice of that list; the rows of at
+// least wave_row entries go to queue (n + 1 entries; *qcount zero before, their number after) and,
+// with long_rows, a second launch sums each by one wave; dedup: the rows are raw sorted lists whose
+// duplicates and self-entries are skipped.  k_bc_sigma raises cnt->err on a sigma beyond the
+// finite range.  k_bc_adj_count also folds the longest row into *longest (atomicMax).
+hipError_t k_bc_adj_count(const DevCsr& out, const DevCsr& in, int64_t n, int64_t* cnt, unsigned long long* longest,
+                          hipStream_t s);
+hipError_t k_bc_adj_fill(const DevCsr& out, const DevCsr& in, int64_t n, const int64_t* soff, int32_t* sadj,
+                         hipStream_t s);
+hipError_t k_bc_level_count(const int32_t* level, int64_t n, int32_t depth, int64_t* hist, Counters* cnt, hipStream_t s);
+hipError_t k_bc_level_scatter(const int32_t* level, int64_t n, int32_t depth, int64_t* cursor, int32_t* order,
+                              Counters* cnt, hipStream_t s);
+hipError_t k_bc_seed(double* sigma, int32_t seed, hipStream_t s);
+hipError_t k_bc_sigma(const int32_t* list, int64_t len, const int64_t* off, const int32_t* adj, bool dedup,
+                      const int32_t* level, int32_t L, double* sigma, int64_t wave_row, int32_t* queue, int64_t* qcount,
+                      bool long_rows, Counters* cnt, hipStream_t s);
+hipError_t k_bc_delta(const int32_t* list, int64_t len, const int64_t* off, const int32_t* adj, bool dedup,
+                      const int32_t* level, int32_t L, const double* sigma, double* delta, double* bc, int64_t wave_row,
+                      int32_t* queue, int64_t* qcount, bool long_rows, hipStream_t s);
 
 // PageRank gather diagnostics: [diag_lo, diag_hi) = only sources in this range are gathered
 // (the others read as 0; results invalid) — attributes the update's time to source ranges.

@@ -411,6 +411,35 @@ class Engine:
         _check(self.lib, self.ctx, self.lib.tgo_copy_scc(self.ctx, L.ptr(out, C.c_int64)))
         return out
 
+    def betweenness(self, seeds=None, directed=False, dense=False, fetch=True):
+        """Brandes' betweenness centrality of a bothE load (tgo_betweenness), over its simple
+        undirected projection or, with directed, over the directed graph of its OUT entries.
+        seeds: Titan ids (dense: row-order indices) whose dependencies are summed in the order
+        given; None = every vertex (exact betweenness).  (bc, info) — bc[v] float64 in row order,
+        the raw sum over ordered pairs (not halved, not normalised; None when fetch is False: the
+        result stays on the device for copy_betweenness / result_rows); info = dict(sources,
+        reached_pairs, max_depth, rounds).  rounds (device launches of the sweeps) is a diagnostic."""
+        a = L.BcArgs(L.SCOPE_BOTH_E, 0, 1 if directed else 0, 1 if dense else 0)
+        info = L.BcInfo()
+        if seeds is None:
+            sd, nseeds = None, -1
+        else:
+            sd = np.ascontiguousarray(seeds, dtype=np.int64)
+            nseeds = len(sd)
+            if nseeds == 0:
+                sd = None
+        out = np.zeros(self.n, dtype=np.float64) if fetch else None
+        _check(self.lib, self.ctx, self.lib.tgo_betweenness(self.ctx, C.byref(a), L.ptr(sd, C.c_int64), nseeds,
+                                                            L.ptr(out, C.c_double), C.byref(info)))
+        return out, {"sources": int(info.sources), "reached_pairs": int(info.reached_pairs),
+                     "max_depth": int(info.max_depth), "rounds": int(info.rounds)}
+
+    def copy_betweenness(self):
+        """The values of the last betweenness() run, in row order."""
+        out = np.zeros(self.n, dtype=np.float64)
+        _check(self.lib, self.ctx, self.lib.tgo_copy_betweenness(self.ctx, L.ptr(out, C.c_double)))
+        return out
+
     def result_rows(self, kind, key_ids, datatypes, relation_id_base):
         """Edgestore entries of the last program's compute keys (tgo_result_rows): the rows
         ResultMode PERSIST writes back (FulgoraGraphComputer.java:248-305)."""
