@@ -382,12 +382,21 @@ int  tgo_copy_multi_distances(tgo_ctx* ctx, int32_t source, int64_t* dist_out);
  * the default.  The two paths add a row's terms in different orders: results at different values
  * agree within the rounding bound of the contract, not bit for bit; at one value they are
  * bit-identical run to run. */
+/* TGO_TUNE_PP_WAVE_ROW / TGO_TUNE_PP_BLOCK_ROW (tgo_peer_pressure): the receive-row length from which a
+ * row is tallied by one wave / by one workgroup instead of its own lane (a row that reaches both goes
+ * to the workgroup); an integer >= 1.  TGO_TUNE_PP_SLOTS: the entries of a wave's LDS tally table, in
+ * [16, 1024] (a workgroup's table has four times as many); a row with more clusters than its table
+ * holds is tallied in passes over classes of its labels.  For all three < 0 = the default, and
+ * every value gives the same clusters, bit for bit.  A row below both lengths is folded by one lane
+ * pairwise, at a cost quadratic in its length: both keys set large (tests do it) leave a hub's row to
+ * a single lane and make a round quadratic in the hub's degree. */
 enum { TGO_TUNE_MS_SPLIT = 1, TGO_TUNE_MS_GHOST = 2, TGO_TUNE_DS_BINS = 3, TGO_TUNE_DS_PILE_CAP = 4,
        TGO_TUNE_DS_DONE = 5, TGO_TUNE_MS_COLD = 6, TGO_TUNE_DS_PULL = 7, TGO_TUNE_DS_SMALL = 8,
        TGO_TUNE_MS_STAY = 9, TGO_TUNE_MS_SPARSE = 10, TGO_TUNE_TRI_WAVE_ROW = 11,
        TGO_TUNE_TRI_BLOCK_ROW = 12, TGO_TUNE_MS_HEAD = 13, TGO_TUNE_CORE_WAVE_ROW = 14,
        TGO_TUNE_CORE_TAIL = 15, TGO_TUNE_CORE_LDS_QUEUE = 16, TGO_TUNE_SCC_WAVE_ROW = 17,
-       TGO_TUNE_SCC_TAIL = 18, TGO_TUNE_SCC_TRIM = 19, TGO_TUNE_SCC_PIVOT = 20, TGO_TUNE_BC_WAVE_ROW = 21 };
+       TGO_TUNE_SCC_TAIL = 18, TGO_TUNE_SCC_TRIM = 19, TGO_TUNE_SCC_PIVOT = 20, TGO_TUNE_BC_WAVE_ROW = 21,
+       TGO_TUNE_PP_WAVE_ROW = 22, TGO_TUNE_PP_BLOCK_ROW = 23, TGO_TUNE_PP_SLOTS = 24 };
 int  tgo_set_tuning(tgo_ctx* ctx, int32_t key, double value);
 
 /* ---- Tracing (the reference's only hook is FulgoraGraphComputer.java:143,307
@@ -555,6 +564,48 @@ int  tgo_betweenness(tgo_ctx* ctx, const tgo_bc_args* args, const int64_t* seeds
                      double* bc_out, tgo_bc_info* info);
 int  tgo_copy_betweenness(tgo_ctx* ctx, double* bc_out);
 
+/* ---- Peer-pressure clustering -------------------------------------------------------------
+ * TinkerPop's PeerPressureVertexProgram over a bothE load, read as the directed multigraph of tgo_scc:
+ * EVERY ENTRY IS ONE EDGE AND CARRIES ONE VOTE.  Parallel entries vote as many times and a self-loop
+ * votes for its own vertex (Fulgora delivers one message per entry) — unlike the simple projection of
+ * tgo_kcore and tgo_betweenness.  A vertex cut counts as its canonical vertex.
+ *   vote_scope = TGO_SCOPE_OUT_E  votes travel along OUT entries and the receiver tallies its IN row
+ *                                 (TinkerPop's default)
+ *                TGO_SCOPE_IN_E   the reverse
+ *                TGO_SCOPE_BOTH_E both rows are tallied
+ * d(v) is the number of entries over which v sends.  The vote strength S(v) is an unsigned 64-bit
+ * integer in units of 2^-32:
+ *   distribute = 0  S(v) = 2^32
+ *   distribute = 1  S(v) = floor(2^32 / d(v)); a vertex with d(v) = 0 sends nothing and never leaves its
+ *                   own cluster (the vertex program's 1.0 / 0.0 is Infinity)
+ * All tallies are exact integer sums, at most (2^31 + 1) 2^32.  THIS IS THE DEVIATION from TinkerPop's
+ * doubles, and it is deliberate: an argmax has no tolerance, and integer tallies make the result
+ * independent of the order of summation.
+ * One round: all vertices update at once from the previous round's clusters,
+ *   T_v(c) = [c = cluster(v)] S(v) + the sum of S(u) over the entries of v's receive rows whose sender u
+ *            has cluster(u) = c,
+ *   cluster'(v) = the c of the largest T_v(c); ties go to the SMALLEST TITAN ID (Titan ids are compared,
+ *            not internal ids or row order).
+ * Initially cluster(v) is v's own (canonical) Titan id.  The program stops after the first round that
+ * changes no vertex (that round counts) and after max_rounds rounds; max_rounds = 0 runs no round.  info:
+ *   rounds        the rounds run; also tgo_stats.iterations.  DETERMINISTIC: unlike the other analytics'
+ *                 rounds it equals the voting supersteps of the vertex program
+ *   changed_last  the vertices the last round changed
+ *   converged     (changed_last == 0 && rounds > 0) || n == 0
+ *   clusters      the distinct labels;  largest: the population of the biggest cluster
+ * The result is unique: bit-identical run to run and for every TGO_TUNE_PP_* value.
+ * args->scope must be TGO_SCOPE_BOTH_E and the loaded scope, args->flags and args->pad 0, args->vote_scope
+ * one of the three, args->distribute 0 or 1, args->max_rounds >= 0 (else TGO_E_INVALID).  Lists that are
+ * not each other's transpose (tgo_load_csr with asymmetric rows) and a partitioned ctx:
+ * TGO_E_UNSUPPORTED.  A failed call leaves the ctx usable.  cluster_out NULL: the result stays on the
+ * device (tgo_copy_peer_pressure; tgo_result_rows kind TGO_RESULT_PEER_PRESSURE).
+ * tgo_copy_peer_pressure after another program: TGO_E_STATE.  The first run builds the ranks of the Titan
+ * ids and their inverse (8 n bytes, tgo_stats.device_bytes) and keeps them with the graph. */
+typedef struct { int32_t scope; int32_t flags; int32_t vote_scope; int32_t distribute; int32_t max_rounds; int32_t pad; } tgo_pp_args;
+typedef struct { int64_t clusters, largest, changed_last; int32_t rounds, converged; } tgo_pp_info;
+int  tgo_peer_pressure(tgo_ctx* ctx, const tgo_pp_args* args, int64_t* cluster_out, tgo_pp_info* info);
+int  tgo_copy_peer_pressure(tgo_ctx* ctx, int64_t* cluster_out);
+
 /* ---- Generic vertex programs ----------------------------------------
  * A vertex program the engine does not implement natively runs its execute() on the host
  * over whole per-vertex vectors (titan_amd/computer.py GenericVertexProgram; the Java host
@@ -666,6 +717,7 @@ int  tgo_dense_ids(tgo_ctx* ctx, const int64_t* titan_ids, int64_t count, int64_
  *   SCC       tgo_scc's label, encoded exactly as COMPONENT
  *   BETWEENNESS  tgo_betweenness's value (Double) on every executed vertex, encoded exactly as
  *             PAGE_RANK; any other typed key: TGO_E_INVALID
+ *   PEER_PRESSURE  tgo_peer_pressure's cluster, encoded exactly as COMPONENT
  * Compute keys are typed property keys of those datatypes, or generic keys (TGO_DT_OBJECT: what
  * getOrCreatePropertyKey makes for a key the program sets without a schema, DefaultSchemaMaker
  * .java:46-48), whose values carry their class (Long 13, Double 20, Integer 12).  Relation ids are
@@ -675,11 +727,12 @@ int  tgo_dense_ids(tgo_ctx* ctx, const int64_t* titan_ids, int64_t count, int64_
  * (the tgo_rows layout, so the rows can be scanned again). */
 typedef enum { TGO_RESULT_DISTANCE = 0, TGO_RESULT_PAGERANK = 1, TGO_RESULT_DEGREE = 2,
                TGO_RESULT_VALUES = 3, TGO_RESULT_COMPONENT = 4, TGO_RESULT_TRIANGLES = 5,
-               TGO_RESULT_CORE = 6, TGO_RESULT_SCC = 7, TGO_RESULT_BETWEENNESS = 8 } tgo_result_kind;
+               TGO_RESULT_CORE = 6, TGO_RESULT_SCC = 7, TGO_RESULT_BETWEENNESS = 8,
+               TGO_RESULT_PEER_PRESSURE = 9 } tgo_result_kind;
 typedef struct {
     int32_t kind;                 /* tgo_result_kind                                          */
     int32_t reserved;             /* TGO_RESULT_VALUES: tgo_value_type of the values           */
-    int64_t key_ids[2];           /* [0] DISTANCE / PAGE_RANK / DEGREE / COMPONENT / TRIANGLES / CORE / SCC / BETWEENNESS key; [1] OUTGOING_EDGE_COUNT / CLUSTERING */
+    int64_t key_ids[2];           /* [0] DISTANCE / PAGE_RANK / DEGREE / COMPONENT / TRIANGLES / CORE / SCC / BETWEENNESS / PEER_PRESSURE key; [1] OUTGOING_EDGE_COUNT / CLUSTERING */
     int32_t datatypes[2];         /* tgo_datatype of each key                                  */
     int64_t relation_id_base;
 } tgo_result_args;

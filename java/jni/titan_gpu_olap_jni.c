@@ -359,6 +359,25 @@ JNIEXPORT jdoubleArray JNICALL JFN(betweenness)(JNIEnv* env, jclass cls, jlong h
     return rc == TGO_OK ? out : NULL;
 }
 
+/* tgo_peer_pressure over the bothE load: every vertex's cluster (a Titan id) in row order, or NULL on
+ * error (the voting rounds are tgo_stats.iterations afterwards; write-back: tgo_result_rows kind
+ * TGO_RESULT_PEER_PRESSURE). */
+static int run_peer_pressure(tgo_ctx* c, const void* a, int64_t* o) {
+    return tgo_peer_pressure(c, (const tgo_pp_args*)a, o, NULL);
+}
+
+JNIEXPORT jlongArray JNICALL JFN(peerPressure)(JNIEnv* env, jclass cls, jlong h, jint vote_scope, jboolean distribute,
+                                               jint max_rounds) {
+    (void)cls;
+    tgo_pp_args a;
+    memset(&a, 0, sizeof a);
+    a.scope = TGO_SCOPE_BOTH_E;
+    a.vote_scope = vote_scope;
+    a.distribute = distribute ? 1 : 0;
+    a.max_rounds = max_rounds;
+    return distances(env, h, run_peer_pressure, &a);
+}
+
 /* tgo_result_rows: Object[5] = {long[] rowKeys, long[] rowEntryBegin, long[] rowByteBegin,
  * long[] entryLimitValuePos, byte[] entryBytes}, or NULL on error (status: lastError; a result
  * beyond the int32 index range of a Java array: IllegalStateException). */

@@ -48,7 +48,8 @@ import java.util.concurrent.Future;
  * (triangles and clustering coefficients of the simple undirected projection, tgo_triangles) and
  * a KCoreVertexProgram (core numbers of the same projection, tgo_kcore),
  * a StronglyConnectedComponentsVertexProgram (bothE read as a directed graph, tgo_scc),
- * a BetweennessCentralityVertexProgram (Brandes' betweenness over either reading, tgo_betweenness).
+ * a BetweennessCentralityVertexProgram (Brandes' betweenness over either reading, tgo_betweenness),
+ * TinkerPop's PeerPressureVertexProgram (one vote per edge, exact integer tallies, tgo_peer_pressure).
  *
  * Write-back (FulgoraGraphComputer.java:248-305): with Persist.VERTEX_PROPERTIES the compute
  * keys are encoded on the device (tgo_result_rows: single-cardinality property entries, one
@@ -549,8 +550,27 @@ public class GpuGraphComputer implements TitanGraphComputer {
                     return new StronglyConnectedComponents();
                 case "com.thinkaurelius.titan.olap.BetweennessCentralityVertexProgram":
                     return new Betweenness(seedsOf(conf), conf.getBoolean("titan.betweenness.directed", false));
+                case "org.apache.tinkerpop.gremlin.process.computer.clustering.peerpressure.PeerPressureVertexProgram":
+                    return new PeerPressure(voteScopeOf(conf), conf.getBoolean("gremlin.peerPressureVertexProgram.distributeVote", false),
+                            conf.getInt("gremlin.peerPressureVertexProgram.maxIterations", 30));
                 default:
                     throw new TitanException("vertex program " + p.getClass().getName() + " is not supported on the GPU path");
+            }
+        }
+
+        /**
+         * The edges a PeerPressureVertexProgram votes along: its default, outE, or what the plain key
+         * titan.peerPressure.edges names (outE, inE, bothE).  A stored edge traversal of its own cannot be
+         * read as a scope and is refused.
+         */
+        private static int voteScopeOf(BaseConfiguration conf) {
+            if (conf.containsKey("gremlin.peerPressureVertexProgram.edgeTraversal") || conf.containsKey("gremlin.peerPressureVertexProgram.incidentTraversal"))
+                throw new TitanException("a PeerPressureVertexProgram with its own edge traversal is not supported on the GPU path");
+            switch (conf.getString("titan.peerPressure.edges", "outE")) {
+                case "outE": return TgoNative.SCOPE_OUT_E;
+                case "inE": return TgoNative.SCOPE_IN_E;
+                case "bothE": return TgoNative.SCOPE_BOTH_E;
+                default: throw new TitanException("titan.peerPressure.edges must be outE, inE or bothE");
             }
         }
 
@@ -803,6 +823,36 @@ public class GpuGraphComputer implements TitanGraphComputer {
         }
         void emit(long[] ids, Map<String, Object> values, FulgoraMapEmitter emitter) {
             double[] c = (double[]) values.get(CENTRALITY);
+            for (int i = 0; i < ids.length; i++) emitter.emit(ids[i], c[i]);
+        }
+    }
+
+    /**
+     * Peer-pressure clustering over bothE (tgo_peer_pressure): every edge carries one vote, parallel edges
+     * and self-loops included; CLUSTER = the Titan id of the vertex's cluster, ties to the smallest id.
+     * Votes are exact integers in units of 2^-32, not doubles.  The iteration reported is the number of
+     * voting rounds run, known after run().
+     */
+    static final class PeerPressure extends DeviceProgram {
+        static final String CLUSTER = "gremlin.peerPressureVertexProgram.cluster";
+        final int voteScope; final boolean distribute; final int maxRounds;
+        private int rounds;
+        PeerPressure(int voteScope, boolean distribute, int maxRounds) {
+            this.voteScope = voteScope; this.distribute = distribute; this.maxRounds = maxRounds;
+        }
+        int scope() { return TgoNative.SCOPE_BOTH_E; }
+        int iterations() { return rounds; }
+        int resultKind() { return TgoNative.RESULT_PEER_PRESSURE; }
+        String[] computeKeys() { return new String[]{CLUSTER}; }
+        int[] computeKeyTypes() { return new int[]{TgoNative.DT_LONG}; }
+        Map<String, Object> run(long ctx) {
+            Map<String, Object> v = new HashMap<>();
+            v.put(CLUSTER, TgoNative.checked(ctx, TgoNative.peerPressure(ctx, voteScope, distribute, maxRounds)));
+            rounds = (int) TgoNative.stats(ctx)[3];
+            return v;
+        }
+        void emit(long[] ids, Map<String, Object> values, FulgoraMapEmitter emitter) {
+            long[] c = (long[]) values.get(CLUSTER);
             for (int i = 0; i < ids.length; i++) emitter.emit(ids[i], c[i]);
         }
     }

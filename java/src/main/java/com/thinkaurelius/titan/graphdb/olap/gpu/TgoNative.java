@@ -110,12 +110,21 @@ public final class TgoNative {
      */
     public static native double[] betweenness(long ctx, long[] seeds, boolean directed);
 
+    /**
+     * tgo_peer_pressure over a bothE load: every vertex's cluster (a Titan id, ties to the smallest) in row
+     * order; voteScope: SCOPE_OUT_E (votes travel along OUT entries), SCOPE_IN_E or SCOPE_BOTH_E; distribute:
+     * a vertex's vote is split over the entries it sends over; maxRounds >= 0.  Every entry is one vote.
+     * null on failure.  stats()[3] then holds the voting rounds run.
+     */
+    public static native long[] peerPressure(long ctx, int voteScope, boolean distribute, int maxRounds);
+
     /** tgo_stats_get: {ghostVertices, truncatedResults, skippedRows, iterations, loadMs, lastKernelMs}. */
     public static native double[] stats(long ctx);
 
     /** tgo_result_kind */
     public static final int RESULT_DISTANCE = 0, RESULT_PAGERANK = 1, RESULT_DEGREE = 2, RESULT_COMPONENT = 4,
-            RESULT_TRIANGLES = 5, RESULT_CORE = 6, RESULT_SCC = 7, RESULT_BETWEENNESS = 8;
+            RESULT_TRIANGLES = 5, RESULT_CORE = 6, RESULT_SCC = 7, RESULT_BETWEENNESS = 8,
+            RESULT_PEER_PRESSURE = 9;
     /**
      * tgo_result_rows: the edgestore entries (single-cardinality property entries) of the last
      * program's compute keys, as {long[] rowKeys, long[] rowEntryBegin, long[] rowByteBegin,

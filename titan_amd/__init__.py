@@ -9,7 +9,7 @@ from .computer import (  # noqa: F401
     BetweennessCentralityVertexProgram, BetweennessRankMapReduce,
     ClusterCountMapReduce, ClusterPopulationMapReduce, ConnectedComponentVertexProgram, CoreSizeMapReduce,
     DegeneracyMapReduce, DegreeCounter, DegreeMapper, ExecutionException, GpuGraph, GpuGraphComputer,
-    KCoreVertexProgram, KeyValue,
+    KCoreVertexProgram, KeyValue, PeerPressureVertexProgram,
     PageRankMapReduce, PageRankVertexProgram, SccSizeMapReduce, ShortestDistanceMapReduce,
     ShortestDistanceVertexProgram, StronglyConnectedComponentsVertexProgram, TitanGraphComputer, TransitivityMapReduce, TriangleCountMapReduce,
     TriangleCountVertexProgram,
@@ -31,4 +31,5 @@ __all__ = [
     "KCoreVertexProgram", "DegeneracyMapReduce", "CoreSizeMapReduce",
     "StronglyConnectedComponentsVertexProgram", "SccSizeMapReduce",
     "BetweennessCentralityVertexProgram", "BetweennessRankMapReduce",
+    "PeerPressureVertexProgram",
 ]

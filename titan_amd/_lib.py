@@ -36,6 +36,7 @@ RESULT_TRIANGLES = 5
 RESULT_CORE = 6
 RESULT_SCC = 7
 RESULT_BETWEENNESS = 8
+RESULT_PEER_PRESSURE = 9
 CC_HOOK, CC_PROPAGATE = 0, 1     # tgo_cc_path
 SSSP_HOP_BOUNDED, SSSP_DELTA = 0, 1
 FLAG_STATS = 1
@@ -50,6 +51,8 @@ TUNE_CORE_WAVE_ROW, TUNE_CORE_TAIL, TUNE_CORE_LDS_QUEUE = 14, 15, 16
 TUNE_SCC_WAVE_ROW, TUNE_SCC_TAIL, TUNE_SCC_TRIM, TUNE_SCC_PIVOT = 17, 18, 19, 20
 # tgo_betweenness: row length from which a wave sums a row (results across values agree within rounding, not bit for bit)
 TUNE_BC_WAVE_ROW = 21
+# tgo_peer_pressure: receive-row lengths of the wave / workgroup tiers, LDS table entries per wave (same clusters for every value)
+TUNE_PP_WAVE_ROW, TUNE_PP_BLOCK_ROW, TUNE_PP_SLOTS = 22, 23, 24
 TRACE_JSON, TRACE_ROCTX = 1, 2   # tgo_trace_enable flags
 DIST_ABSENT = -(1 << 63)
 ABI_VERSION = 2
@@ -184,6 +187,16 @@ class BcInfo(C.Structure):
     _fields_ = [("sources", C.c_int64), ("reached_pairs", C.c_int64), ("max_depth", C.c_int32), ("rounds", C.c_int32)]
 
 
+class PpArgs(C.Structure):
+    _fields_ = [("scope", C.c_int32), ("flags", C.c_int32), ("vote_scope", C.c_int32), ("distribute", C.c_int32),
+                ("max_rounds", C.c_int32), ("pad", C.c_int32)]
+
+
+class PpInfo(C.Structure):
+    _fields_ = [("clusters", C.c_int64), ("largest", C.c_int64), ("changed_last", C.c_int64),
+                ("rounds", C.c_int32), ("converged", C.c_int32)]
+
+
 class GatherArgs(C.Structure):
     _fields_ = [("scope", C.c_int32), ("value_type", C.c_int32), ("combiner", C.c_int32), ("edge_fn", C.c_int32)]
 
@@ -214,6 +227,7 @@ EXPORTS = [
     "tgo_gather_lists", "tgo_result_rows_values", "tgo_set_edge_program",
     "tgo_components", "tgo_copy_components", "tgo_triangles", "tgo_copy_triangles",
     "tgo_kcore", "tgo_copy_cores", "tgo_scc", "tgo_copy_scc", "tgo_betweenness", "tgo_copy_betweenness",
+    "tgo_peer_pressure", "tgo_copy_peer_pressure",
     "tgo_rmat_edges", "tgo_rmat_edges_device", "tgo_rmat_partition_device", "tgo_pick_roots", "tgo_synth_rows",
     # titan_gpu_olap_part.h (1-D vertex-partitioned multi-GPU)
     "tgo_load_partition", "tgo_part_layout", "tgo_load_partition_layout", "tgo_part_bfs_begin", "tgo_part_bfs_td", "tgo_part_bfs_claim", "tgo_part_bfs_bu",
@@ -280,6 +294,8 @@ def load() -> C.CDLL:
         "tgo_copy_scc": (C.c_int, [vp, _i64p]),
         "tgo_betweenness": (C.c_int, [vp, P(BcArgs), _i64p, C.c_int64, C.POINTER(C.c_double), P(BcInfo)]),
         "tgo_copy_betweenness": (C.c_int, [vp, C.POINTER(C.c_double)]),
+        "tgo_peer_pressure": (C.c_int, [vp, P(PpArgs), _i64p, P(PpInfo)]),
+        "tgo_copy_peer_pressure": (C.c_int, [vp, _i64p]),
         "tgo_pagerank": (C.c_int, [vp, P(PrArgs), C.POINTER(C.c_double)]),
         "tgo_walkcount": (C.c_int, [vp, C.c_int32, _i32p]),
         "tgo_stats_get": (C.c_int, [vp, P(Stats)]),

@@ -477,6 +477,52 @@ class BetweennessCentralityVertexProgram(VertexProgram):
         return BetweennessCentralityVertexProgram.Builder()
 
 
+class PeerPressureVertexProgram(VertexProgram):
+    """TinkerPop's PeerPressureVertexProgram over bothE (tgo_peer_pressure): every edge carries one
+    vote, parallel edges and self-loops included.  CLUSTER = the Titan id of the vertex's cluster
+    (Long), ties to the smallest id.  distributeVote(True) splits a vertex's vote over the edges it
+    sends over; maxIterations(n) bounds the voting rounds (default 30); edges(scope_name): the edges
+    votes travel along ("outE", TinkerPop's default, "inE" or "bothE").  Votes are exact integers
+    in units of 2^-32, not doubles, so the result does not depend on the order of summation.
+    memory.getIteration() reports the voting rounds run.  Result graph and persist preference as
+    ShortestDistanceVertexProgram."""
+    CLUSTER = "gremlin.peerPressureVertexProgram.cluster"
+    compute_keys = (CLUSTER,)
+    scope_name = "bothE"
+
+    def __init__(self, distribute=False, max_iterations=30, edges="outE"):
+        if edges not in SCOPE_NAMES:
+            raise TitanException(L.TGO_E_INVALID, f"unknown edge scope {edges!r}")
+        self.distribute = bool(distribute)
+        self.max_iterations = int(max_iterations)
+        self.edges = edges
+
+    class Builder:
+        def __init__(self):
+            self._distribute = False
+            self._max = 30
+            self._edges = "outE"
+
+        def distributeVote(self, on=True):  # noqa: N802
+            self._distribute = bool(on)
+            return self
+
+        def maxIterations(self, n):  # noqa: N802
+            self._max = int(n)
+            return self
+
+        def edges(self, scope_name):
+            self._edges = scope_name
+            return self
+
+        def create(self, graph=None):
+            return PeerPressureVertexProgram(self._distribute, self._max, self._edges)
+
+    @staticmethod
+    def build():
+        return PeerPressureVertexProgram.Builder()
+
+
 # ----------------------------------------------------------------------------- map-reduces
 class MapReduce:
     memory_key = ""
@@ -551,8 +597,14 @@ class _MemoryKeyBuilder:
         return self._cls(self._k)
 
 
+def _cluster_labels(props):
+    """PeerPressureVertexProgram.CLUSTER when the program set it, else the component labels."""
+    lab = props.get(PeerPressureVertexProgram.CLUSTER)
+    return props.get(ConnectedComponentVertexProgram.COMPONENT) if lab is None else lab
+
+
 class ClusterPopulationMapReduce(MapReduce):
-    """Component label -> number of vertices carrying it."""
+    """Cluster (or component) label -> number of vertices carrying it."""
     DEFAULT_MEMORY_KEY = "clusterPopulation"
 
     def __init__(self, key=DEFAULT_MEMORY_KEY):
@@ -563,7 +615,7 @@ class ClusterPopulationMapReduce(MapReduce):
         return _MemoryKeyBuilder(ClusterPopulationMapReduce)
 
     def emit(self, ids, props):
-        lab = props.get(ConnectedComponentVertexProgram.COMPONENT)
+        lab = _cluster_labels(props)
         if lab is None:
             return {}
         u, c = np.unique(np.asarray(lab, dtype=np.int64), return_counts=True)
@@ -571,7 +623,7 @@ class ClusterPopulationMapReduce(MapReduce):
 
 
 class ClusterCountMapReduce(MapReduce):
-    """Number of distinct component labels."""
+    """Number of distinct cluster (or component) labels."""
     DEFAULT_MEMORY_KEY = "clusterCount"
 
     def __init__(self, key=DEFAULT_MEMORY_KEY):
@@ -582,7 +634,7 @@ class ClusterCountMapReduce(MapReduce):
         return _MemoryKeyBuilder(ClusterCountMapReduce)
 
     def emit(self, ids, props):
-        lab = props.get(ConnectedComponentVertexProgram.COMPONENT)
+        lab = _cluster_labels(props)
         return 0 if lab is None else int(len(np.unique(np.asarray(lab, dtype=np.int64))))
 
 
@@ -847,7 +899,8 @@ class GpuGraphComputer(TitanGraphComputer):
                     StronglyConnectedComponentsVertexProgram: (L.RESULT_SCC,
                                                                (StronglyConnectedComponentsVertexProgram.COMPONENT,)),
                     BetweennessCentralityVertexProgram: (L.RESULT_BETWEENNESS,
-                                                         (BetweennessCentralityVertexProgram.CENTRALITY,))}
+                                                         (BetweennessCentralityVertexProgram.CENTRALITY,)),
+                    PeerPressureVertexProgram: (L.RESULT_PEER_PRESSURE, (PeerPressureVertexProgram.CLUSTER,))}
 
     def _result_mode(self):
         """resultMode if set, else the program's preferred (ResultGraph, Persist) as Fulgora
@@ -964,6 +1017,12 @@ class GpuGraphComputer(TitanGraphComputer):
             eng = self.graph.engine_for(L.SCOPE_BOTH_E)
             props[BetweennessCentralityVertexProgram.CENTRALITY], info = eng.betweenness(p.seeds, directed=p.directed)
             iteration = info["sources"]
+            ids = eng.vertex_ids()
+        elif isinstance(p, PeerPressureVertexProgram):
+            eng = self.graph.engine_for(L.SCOPE_BOTH_E)
+            props[PeerPressureVertexProgram.CLUSTER], info = eng.peer_pressure(
+                SCOPE_NAMES[p.edges], distribute=p.distribute, max_rounds=p.max_iterations)
+            iteration = info["rounds"]
             ids = eng.vertex_ids()
         else:
             raise TitanException(L.TGO_E_UNSUPPORTED, f"vertex program {type(p).__name__} is not supported on the GPU path")

@@ -203,6 +203,18 @@ int tgo_set_tuning(tgo_ctx* ctx, int32_t key, double value) {
             return fail(ctx, TGO_E_INVALID, "TGO_TUNE_BC_WAVE_ROW: a row length >= 1 (< 0: the default)");
         ctx->bc_wave_row = value < 0.0 ? -1 : static_cast<int64_t>(value);
         return TGO_OK;
+    case TGO_TUNE_PP_WAVE_ROW:
+    case TGO_TUNE_PP_BLOCK_ROW:
+        if (!(value < 0.0) && !(value >= 1.0 && value <= 9.0e15 && value == static_cast<double>(static_cast<int64_t>(value))))
+            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_PP_WAVE_ROW / _BLOCK_ROW: a row length >= 1 (< 0: the default)");
+        (key == TGO_TUNE_PP_WAVE_ROW ? ctx->pp_wave_row : ctx->pp_block_row) = value < 0.0 ? -1 : static_cast<int64_t>(value);
+        return TGO_OK;
+    case TGO_TUNE_PP_SLOTS:
+        if (!(value < 0.0) && !(value >= static_cast<double>(kPpMinSlots) && value <= static_cast<double>(kPpMaxSlots) &&
+                                value == static_cast<double>(static_cast<int64_t>(value))))
+            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_PP_SLOTS: table entries per wave in [16, 1024] (< 0: the default)");
+        ctx->pp_slots = value < 0.0 ? -1 : static_cast<int64_t>(value);
+        return TGO_OK;
     default:
         return fail(ctx, TGO_E_INVALID, "tgo_set_tuning: unknown key");
     }

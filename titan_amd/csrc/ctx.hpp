@@ -94,6 +94,9 @@ struct tgo_ctx {
     int scc_pivot = -1;         // (< 0: the defaults kSccWaveRow / kSccTailDefault, both phases on)
     int64_t bc_wave_row = -1;   // tgo_set_tuning(TGO_TUNE_BC_WAVE_ROW): row length from which a wave sums it
                                 // (< 0: the default kBcWaveRow)
+    int64_t pp_wave_row = -1;   // tgo_set_tuning(TGO_TUNE_PP_WAVE_ROW / _BLOCK_ROW): receive-row lengths from which
+    int64_t pp_block_row = -1;  // a wave / a workgroup tallies the row; TGO_TUNE_PP_SLOTS: table entries per wave
+    int64_t pp_slots = -1;      // (< 0: the defaults kPpWaveRow / kPpBlockRow / kPpSlots)
     // state a native partitioned driver keeps between runs on this graph (part_driver.cpp:
     // the PageRank ghost lists); dropped with the graph
     std::shared_ptr<void> part_state;

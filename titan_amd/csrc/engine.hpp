@@ -486,6 +486,9 @@ struct DevGraph {
     int64_t* bc_soff = nullptr;     // n + 1
     int32_t* bc_sadj = nullptr;     // bc_snnz
     int64_t bc_snnz = 0, bc_smax = 0;   // its entries and its longest row
+    // ranks of the Titan ids among the executed vertices (tgo_peer_pressure, built on its first run)
+    int32_t* pp_rank = nullptr;     // n: internal index -> rank
+    int32_t* pp_inv = nullptr;      // n: rank -> internal index
 };
 
 // Views of the loaded scope.
@@ -1032,6 +1035,29 @@ hipError_t k_bc_sigma(const int32_t* list, int64_t len, const int64_t* off, cons
 hipError_t k_bc_delta(const int32_t* list, int64_t len, const int64_t* off, const int32_t* adj, bool dedup,
                       const int32_t* level, int32_t L, const double* sigma, double* delta, double* bc, int64_t wave_row,
                       int32_t* queue, int64_t* qcount, bool long_rows, hipStream_t s);
+
+// Peer-pressure clustering (pp.hip).  A round's votes are one array indexed by sender: int32 labels
+// (distribute = 0) or 8-byte words label << 33 | S (distribute = 1); labels are ranks of the Titan ids.
+// k_pp_init: the first votes into cur and the rows of at least wave_row / block_row receive entries
+// into wq / bq (n + 1 entries each; cnt->qlen / cnt->mf, zero before, their numbers after).
+// k_pp_round: the next votes from cur into next of one tier's rows (0: the rows in neither queue, 1: the
+// wave queue, 2: the block queue; first: round 1, where every sender still has its own label);
+// cnt->red[0] += the vertices that moved.  k_pp_finish: label = the clusters'
+// Titan ids, hist (n words, zero before) = their populations, cnt->qlen += the clusters, cnt->red[0]
+// = the largest population.
+constexpr int32_t kPpMinSlots = 16, kPpMaxSlots = 1024;     // TGO_TUNE_PP_SLOTS: table entries per wave
+struct PpRun {
+    View recv;                  // the rows a vertex tallies
+    int64_t n = 0, wave_row = 0, block_row = 0;
+    int32_t slots = 0;
+    bool distribute = false;
+    int32_t *wq = nullptr, *bq = nullptr;
+    int64_t nwave = 0, nblock = 0;
+};
+hipError_t k_pp_init(const PpRun& r, const View& send, const int32_t* rank, void* cur, Counters* cnt, hipStream_t s);
+hipError_t k_pp_round(const PpRun& r, bool first, int tier, const void* cur, void* next, Counters* cnt, hipStream_t s);
+hipError_t k_pp_finish(const PpRun& r, const void* cur, const int32_t* inv, const int64_t* tid, int64_t* label, int32_t* hist,
+                       Counters* cnt, hipStream_t s);
 
 // PageRank gather diagnostics: [diag_lo, diag_hi) = only sources in this range are gathered
 // (the others read as 0; results invalid) — attributes the update's time to source ranges.

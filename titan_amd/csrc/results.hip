@@ -74,7 +74,7 @@ __device__ inline bool value_of(const ResArgs& a, const void* v0, const void* v1
         return true;
     }
     if (a.kind == TGO_RESULT_COMPONENT || a.kind == TGO_RESULT_CORE || a.kind == TGO_RESULT_SCC ||
-        a.kind == TGO_RESULT_BETWEENNESS) {   // a label / core number / centrality (raw bits) on every executed vertex
+        a.kind == TGO_RESULT_BETWEENNESS || a.kind == TGO_RESULT_PEER_PRESSURE) {   // a label / core number / centrality (raw bits) on every executed vertex
         bits = static_cast<const uint64_t*>(v0)[v];
         return true;
     }
@@ -186,16 +186,16 @@ int encode_results(const ResultSource& src, const tgo_result_args* a, const int3
     ra.kind = a->kind;
     ra.nkeys = a->kind == TGO_RESULT_PAGERANK || a->kind == TGO_RESULT_TRIANGLES ? 2 : 1;
     ra.rel_base = a->relation_id_base;
-    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_BETWEENNESS) { err = "unknown result kind"; return TGO_E_INVALID; }
-    int want[9][2] = {{TGO_DT_LONG, 0}, {TGO_DT_DOUBLE, TGO_DT_DOUBLE}, {TGO_DT_INTEGER, 0}, {0, 0}, {TGO_DT_LONG, 0},
-                      {TGO_DT_LONG, TGO_DT_DOUBLE}, {TGO_DT_LONG, 0}, {TGO_DT_LONG, 0}, {TGO_DT_DOUBLE, 0}};
+    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_PEER_PRESSURE) { err = "unknown result kind"; return TGO_E_INVALID; }
+    int want[10][2] = {{TGO_DT_LONG, 0}, {TGO_DT_DOUBLE, TGO_DT_DOUBLE}, {TGO_DT_INTEGER, 0}, {0, 0}, {TGO_DT_LONG, 0},
+                       {TGO_DT_LONG, TGO_DT_DOUBLE}, {TGO_DT_LONG, 0}, {TGO_DT_LONG, 0}, {TGO_DT_DOUBLE, 0}, {TGO_DT_LONG, 0}};
     // StandardSerializer registration numbers of the value classes (:71-81): Long 13, Double 20, Integer 12
     // (per key where a kind's two keys differ: the triangle count is a Long, its coefficient a Double)
-    uint8_t reg[9][2] = {{0x80 | 13, 0}, {0x80 | 20, 0x80 | 20}, {0x80 | 12, 0}, {0, 0}, {0x80 | 13, 0},
-                         {0x80 | 13, 0x80 | 20}, {0x80 | 13, 0}, {0x80 | 13, 0}, {0x80 | 20, 0}};
-    static_assert(TGO_RESULT_BETWEENNESS == 8, "want / reg hold one row per result kind");
+    uint8_t reg[10][2] = {{0x80 | 13, 0}, {0x80 | 20, 0x80 | 20}, {0x80 | 12, 0}, {0, 0}, {0x80 | 13, 0},
+                          {0x80 | 13, 0x80 | 20}, {0x80 | 13, 0}, {0x80 | 13, 0}, {0x80 | 20, 0}, {0x80 | 13, 0}};
+    static_assert(TGO_RESULT_PEER_PRESSURE == 9, "want / reg hold one row per result kind");
     const bool long_or_int = a->kind == TGO_RESULT_COMPONENT || a->kind == TGO_RESULT_TRIANGLES || a->kind == TGO_RESULT_CORE ||
-                             a->kind == TGO_RESULT_SCC;
+                             a->kind == TGO_RESULT_SCC || a->kind == TGO_RESULT_PEER_PRESSURE;
     if (long_or_int) {
         // the labels / counts / core numbers are longs: a Long key, an Integer key (the caller checked the range)
         // or a generic key holding Longs — the int64 encoder of a generic program's values
@@ -231,7 +231,7 @@ int encode_results(const ResultSource& src, const tgo_result_args* a, const int3
             lead[k] = reg[a->kind][k];                     // generic key: writeClassAndObject
         } else if (a->datatypes[k] != want[a->kind][k]) {
             err = "compute key datatype must be Long (distance), Double (pageRank, edgeCount, clustering coefficient), "
-                  "Integer (degree), Long or Integer (component, triangles, core number), Double (betweenness) or generic (Object)";
+                  "Integer (degree), Long or Integer (component, cluster, triangles, core number), Double (betweenness) or generic (Object)";
             return TGO_E_UNSUPPORTED;
         }
     }

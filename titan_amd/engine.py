@@ -440,6 +440,29 @@ class Engine:
         _check(self.lib, self.ctx, self.lib.tgo_copy_betweenness(self.ctx, L.ptr(out, C.c_double)))
         return out
 
+    def peer_pressure(self, vote_scope=L.SCOPE_OUT_E, distribute=False, max_rounds=30, fetch=True):
+        """Peer-pressure clustering of a bothE load (tgo_peer_pressure): every entry is one edge and one
+        vote (parallel entries and self-loops count).  vote_scope: votes travel along OUT entries
+        (TinkerPop's default), IN entries or both; distribute: a vertex's vote is split over the d(v)
+        entries it sends over (floor(2^32 / d(v)) in units of 2^-32; tallies are exact integers);
+        max_rounds: TinkerPop's maxIterations.  (cluster, info) — cluster[v] = the Titan id of v's
+        cluster in row order, ties to the smallest Titan id (None when fetch is False: the result
+        stays on the device for copy_peer_pressure / result_rows); info = dict(clusters, largest,
+        changed_last, rounds, converged), all deterministic."""
+        a = L.PpArgs(L.SCOPE_BOTH_E, 0, int(vote_scope), 1 if distribute else 0, int(max_rounds), 0)
+        info = L.PpInfo()
+        out = np.zeros(self.n, dtype=np.int64) if fetch else None
+        _check(self.lib, self.ctx, self.lib.tgo_peer_pressure(self.ctx, C.byref(a), L.ptr(out, C.c_int64), C.byref(info)))
+        return out, {"clusters": int(info.clusters), "largest": int(info.largest),
+                     "changed_last": int(info.changed_last), "rounds": int(info.rounds),
+                     "converged": int(info.converged)}
+
+    def copy_peer_pressure(self):
+        """The clusters of the last peer_pressure() run, in row order."""
+        out = np.zeros(self.n, dtype=np.int64)
+        _check(self.lib, self.ctx, self.lib.tgo_copy_peer_pressure(self.ctx, L.ptr(out, C.c_int64)))
+        return out
+
     def result_rows(self, kind, key_ids, datatypes, relation_id_base):
         """Edgestore entries of the last program's compute keys (tgo_result_rows): the rows
         ResultMode PERSIST writes back (FulgoraGraphComputer.java:248-305)."""
