@@ -193,6 +193,15 @@ int tgo_part_active_rows(tgo_ctx* ctx, int64_t* n_active);
  * *hot_per_rank = 0: blocking not applicable (bothE load, TGO_PR_BLOCKED=0, too small) —
  * keep the plain layout.  Building is host work on the downloaded in-lists (load time). */
 int tgo_part_pr_blocked(tgo_ctx* ctx, int32_t world, int64_t active_span, int64_t* hot_per_rank);
+/* The fixed-point range of the blocked layout (tgo_part_pr_exact_check) is one per JOB: it
+ * comes from the longest in-row of any rank, because a rank whose own rows are short would
+ * otherwise emit contributions that the peer summing a long row cannot add exactly.  Before
+ * tgo_part_pr_blocked a driver all-reduces (MAX) every rank's tgo_part_pr_longest_row and hands
+ * the result to tgo_part_pr_set_longest_row (TGO_E_INVALID when shorter than the rank's own; a
+ * rank that is never told uses its own rows, which is right for world = 1 only).  A layout
+ * built for another length is rebuilt.  tgo_part_pagerank_run does this itself. */
+int tgo_part_pr_longest_row(tgo_ctx* ctx, int64_t* longest_row);
+int tgo_part_pr_set_longest_row(tgo_ctx* ctx, int64_t longest_row);
 int tgo_part_pr_step_cold(tgo_ctx* ctx, const double* gathered);
 int tgo_part_pr_step_hot(tgo_ctx* ctx, const double* gathered, double* contrib_local);
 
@@ -236,7 +245,8 @@ int  tgo_part_msbfs_run(tgo_ctx* ctx, tgo_exchange* x, const int64_t* seeds, int
  *                         minimum moves the bucket.  delta <= 0: the maximum of the ranks'
  *                         default widths.  *phases = relax phases run.
  *   tgo_part_pagerank_run PageRankVertexProgram (distributed_pagerank): layout agreed with an
- *                         all-reduce(MAX) of the active rows, tgo_part_pr_blocked, then per
+ *                         all-reduce(MAX) of the active rows and of the longest in-row
+ *                         (tgo_part_pr_set_longest_row), tgo_part_pr_blocked, then per
  *                         update the gathered vector refreshed by exchange_mode 0 = all-gather
  *                         of every rank's slices, 1 = ghost exchange: only the contributions
  *                         this rank's in-lists read (lists built once per layout and kept with

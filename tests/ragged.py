@@ -14,7 +14,15 @@ ragged_graph(n, seed) is made of
     longer than nb and holds duplicates.
 The roles are spread over the dense indices by a random permutation; weights are int32 in
 [0, 40]; the Titan ids are strictly increasing, non-contiguous multiples of 8.
+
+For the partitioned path (test_ragged_part_cpu.py, test_gpu_ragged_part.py): padded_ragged pads
+a ragged graph to whole bitmap words, part_cases names the partitions that put a rank on one
+word, on the final word and on nothing but entry-less slots (the only helper here that imports
+the product, for SlotPartition, and only when called), and range_fixture / range_reference are
+the two-rank PageRank job whose ranks' fixed-point ranges differ, with its exact ranks.
 """
+from fractions import Fraction
+
 import numpy as np
 
 # one below / on / one above: kSerialRow 32 (cc.hip), the wave width and kCoop 64 (msbfs.hip),
@@ -122,3 +130,76 @@ def edge_fixed_point(ids, src, dst):
     src = np.asarray(src, np.int64)
     dst = np.asarray(dst, np.int64)
     return numpy_fixed_point(ids, np.concatenate([src, dst]), np.concatenate([dst, src]))
+
+
+# ----------------------------------------------------------------------------- partitions
+def padded_ragged(n, seed):
+    """ragged_graph(n, seed) padded with entry-less vertices to whole 64-vertex words:
+    (P, src, dst, w, info), P = 64 * ceil(n / 64); the dense indices n..P-1 are pads."""
+    src, dst, w, _, info = ragged_graph(n, seed)
+    return 64 * ((n + 63) // 64), src, dst, w, info
+
+
+def part_cases(P, src, dst):
+    """[(name, SlotPartition)] over the padded graph.  P = 4160 (n = 4099): a single rank; a
+    rank that owns one bitmap word; a last rank that owns the final word (3 real vertices and 61
+    pads); entry-balanced ranges; and `empty`, which appends 64 more pads and gives them to a
+    rank of their own (part.n = P + 64), a rank without any entry.  P = 1024: equal ranges."""
+    from titan_amd.distributed import SlotPartition, word_weights
+    if P == 1024:
+        return [("equal2", SlotPartition.equal(P, 2)), ("equal4", SlotPartition.equal(P, 4))]
+    assert P == 4160, P
+    return [("single", SlotPartition([0, P], P)),
+            ("one_word", SlotPartition([0, 64, P], P)),
+            ("last_word", SlotPartition([0, 2112, 4096, P], P)),
+            ("balanced4", SlotPartition.balanced(word_weights(src, dst, 0, P), 4)),
+            ("empty", SlotPartition([0, 2112, P, P + 64], P + 64))]
+
+
+def part_case(P, src, dst, name):
+    return dict(part_cases(P, src, dst))[name]
+
+
+def owner(part, v):
+    """The rank that owns caller id v."""
+    return int(np.searchsorted(part.bounds, v, side="right") - 1)
+
+
+# ----------------------------------------------------------------------------- cross-rank range
+RANGE_S = 32832                 # vertices per rank: 513 bitmap words
+RANGE_D = 32769                 # sources of the long row: 2^15 + 1, so 2^16 is the first power that holds it
+RANGE_ALPHA = Fraction(5, 2)
+
+
+def range_fixture():
+    """(n, src, dst, t): two equal ranges of S vertices.  Rank 0 owns t = 0 and nothing else with
+    an entry; rank 1 owns D sources s_i = S + i, each with a self-loop and an edge s_i -> t.  Over
+    inE the longest in-row of rank 0 (t's) has D entries and that of rank 1 has one."""
+    s = RANGE_S + np.arange(RANGE_D, dtype=np.int64)
+    src = np.concatenate([s, s]).astype(np.int32)
+    dst = np.concatenate([s, np.zeros(RANGE_D, np.int64)]).astype(np.int32)
+    return 2 * RANGE_S, src, dst, 0
+
+
+def range_contributions(iters):
+    """[c_1 .. c_iters] of a source as Fractions: x_1 = 1/n, c_k = x_k / 2 (edgeCount 2),
+    x_{k+1} = alpha c_k + (1 - alpha) / n (the self-loop is the source's only in-entry)."""
+    n = 2 * RANGE_S
+    base = (1 - RANGE_ALPHA) / n
+    x, c = Fraction(1, n), []
+    for _ in range(iters):
+        c.append(x / 2)
+        x = RANGE_ALPHA * c[-1] + base
+    return c
+
+
+def range_reference(iters):
+    """The exact ranks after `iters` iterations, rounded once to float64: every source holds
+    x_iters, t holds alpha D c_{iters-1} + (1 - alpha) / n, every other vertex (1 - alpha) / n."""
+    n = 2 * RANGE_S
+    base = (1 - RANGE_ALPHA) / n
+    c = range_contributions(iters)
+    pr = np.full(n, float(base))
+    pr[RANGE_S:RANGE_S + RANGE_D] = float(2 * c[iters - 1])
+    pr[0] = float(RANGE_ALPHA * RANGE_D * c[iters - 2] + base)
+    return pr

@@ -308,6 +308,15 @@ class NumpyPartBackend:
         act = [v for v in range(self.n_local) if self.out[v] or self.inn[v]]
         return act[-1] + 1 if act else 0
 
+    job_row = 0         # tgo_part_pr_set_longest_row: the longest in-row of any rank, as agreed
+
+    def pr_longest_row(self):
+        return max(map(len, self.inn), default=0)
+
+    def pr_set_longest_row(self, longest_row):
+        assert longest_row >= self.pr_longest_row()
+        self.job_row = longest_row
+
     def pr_layout(self, world, span):
         """tgo_part_pr_blocked's contract: the hot-first gathered layout of world * span."""
         self.world, self.span = world, span

@@ -234,7 +234,7 @@ EXPORTS = [
     "tgo_part_bfs_end", "tgo_part_pr_begin", "tgo_part_pr_step", "tgo_part_pr_end", "tgo_part_pr_exact_check", "tgo_part_pr_plain",
     "tgo_part_weight_min", "tgo_load_partition_rows", "tgo_finish_partition_rows",
     "tgo_rmat_partition",
-    "tgo_part_active_rows", "tgo_part_pr_blocked", "tgo_part_device_counts", "tgo_part_set_local_qlen", "tgo_part_ms_pack_dev", "tgo_part_pr_step_cold", "tgo_part_pr_step_hot",
+    "tgo_part_active_rows", "tgo_part_pr_blocked", "tgo_part_pr_longest_row", "tgo_part_pr_set_longest_row", "tgo_part_device_counts", "tgo_part_set_local_qlen", "tgo_part_ms_pack_dev", "tgo_part_pr_step_cold", "tgo_part_pr_step_hot",
     "tgo_part_ms_begin", "tgo_part_ms_pull", "tgo_part_ms_push", "tgo_part_ms_settle", "tgo_part_ms_end",
     "tgo_part_ms_pack", "tgo_part_ms_settle_pairs", "tgo_part_ms_pack_fixed", "tgo_part_ms_settle_fixed",
     "tgo_part_ms_source_counts", "tgo_part_ms_source_entries", "tgo_part_ms_push_masked", "tgo_part_ms_or_fixed",
@@ -355,6 +355,8 @@ def load() -> C.CDLL:
         "tgo_load_partition_rows": (C.c_int, [vp, vp, P(Rows), P(Schema), P(LoadOpts), C.c_int32, _i64p]),
         "tgo_finish_partition_rows": (C.c_int, [vp, vp, C.c_int32, _i64p]),
         "tgo_part_active_rows": (C.c_int, [vp, _i64p]),
+        "tgo_part_pr_longest_row": (C.c_int, [vp, _i64p]),
+        "tgo_part_pr_set_longest_row": (C.c_int, [vp, C.c_int64]),
         "tgo_part_device_counts": (C.c_int, [vp, vp]),
         "tgo_part_set_local_qlen": (C.c_int, [vp, C.c_int64]),
         "tgo_part_ms_pack_dev": (C.c_int, [vp, vp, C.c_int32, vp, vp]),

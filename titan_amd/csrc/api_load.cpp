@@ -111,10 +111,12 @@ static void fx_range(int64_t max_len, int& elo, int& ehi) {
 // Cache-blocked PageRank in-lists of the rows [0, n_rows) (rows past n_rows have no entries)
 // over sources [0, n_src): built on the device from the uploaded in-lists (d_off / d_adj,
 // pr_layout.hip) unless TGO_HOST_ASSEMBLY=1 (or a row is not sorted by source), then on the
-// host; uploaded into cb.
+// host; uploaded into cb.  job_row: the longest in-row of the whole job where `off` holds one
+// rank's rows of it — the fixed-point range comes from the longer of the two, so every rank of a
+// partitioned job checks what it emits against the range of the rank that sums the longest row.
 int upload_cold_blocks(tgo_ctx* ctx, const std::vector<int64_t>& off, const std::vector<int32_t>& adj,
                        int64_t n_src, int64_t hot, int64_t n_rows, ColdBlocks& cb, bool& ready,
-                       const int64_t* d_off, const int32_t* d_adj, int64_t d_nnz, int64_t win) {
+                       const int64_t* d_off, const int32_t* d_adj, int64_t d_nnz, int64_t win, int64_t job_row) {
     cb = ColdBlocks();
     ready = false;
     HostColdBlocks hc;
@@ -304,7 +306,7 @@ int upload_cold_blocks(tgo_ctx* ctx, const std::vector<int64_t>& off, const std:
     cb.n_crows = static_cast<int64_t>(hc.crow.size());
     HIP_TRY(upload(ctx, cb.crow, hc.crow));
     if (cb.fx || cb.cfx) {                          // the fixed-point passes' range flag (FxGuard)
-        int64_t max_len = 0;
+        int64_t max_len = job_row;
         for (size_t r = 0; r + 1 < off.size(); ++r) max_len = std::max(max_len, off[r + 1] - off[r]);
         fx_range(max_len, cb.fx_elo, cb.fx_ehi);
         HIP_TRY(dev_alloc(ctx, cb.fx_bad, 1));
@@ -465,12 +467,16 @@ static int upload_graph(tgo_ctx* ctx, HostGraph& h, bool allow_segments = true) 
 int part_upload(tgo_ctx* ctx, HostGraph& h, int64_t n_global, int64_t lo) {
     free_graph(ctx);
     ctx->staging = RowStaging();
+    int64_t max_in = 0;
+    for (size_t r = 0; r + 1 < h.in.off.size(); ++r) max_in = std::max(max_in, h.in.off[r + 1] - h.in.off[r]);
     int rc = upload_graph(ctx, h, false);     // partitioned PageRank gathers global ids: plain CSR
     if (rc) return rc;
     ctx->g.partitioned = true;
     ctx->part_pr_world = 0;
     ctx->part_pr_plain = false;
     ctx->part_pr_hot = ctx->part_pr_span = 0;
+    ctx->part_max_in_row = max_in;
+    ctx->part_pr_job_row = ctx->part_pr_built_row = 0;
     ctx->part_pr_iter = ctx->part_pr_iters = 0;
     ctx->g.lo = lo;
     ctx->g.n_global = n_global;

@@ -620,6 +620,25 @@ int tgo_part_active_rows(tgo_ctx* ctx, int64_t* n_active) {
     return TGO_OK;
 }
 
+// The longest in-row of this rank's rows, and the longest of any rank as the driver agreed it
+// (all-reduce MAX) before tgo_part_pr_blocked: the blocked layout's fixed-point range comes from it.
+int tgo_part_pr_longest_row(tgo_ctx* ctx, int64_t* longest_row) {
+    int rc = part_check(ctx);
+    if (rc) return rc;
+    if (!longest_row) return fail(ctx, TGO_E_INVALID, "null argument");
+    *longest_row = ctx->part_max_in_row;
+    return TGO_OK;
+}
+
+int tgo_part_pr_set_longest_row(tgo_ctx* ctx, int64_t longest_row) {
+    int rc = part_check(ctx);
+    if (rc) return rc;
+    if (longest_row < ctx->part_max_in_row)
+        return fail(ctx, TGO_E_INVALID, "tgo_part_pr_set_longest_row: shorter than this rank's longest in-row");
+    ctx->part_pr_job_row = longest_row;
+    return TGO_OK;
+}
+
 // Cache-blocked partitioned PageRank.  The gathered contribution vector is laid out hot-first
 // across ranks: [rank 0 rows 0..H) ... [rank W-1 rows 0..H) | [rank 0 rows H..A) ... — the
 // degree-grouped layout puts each rank's hottest rows first and its entry-less rows last, so
@@ -641,7 +660,12 @@ int tgo_part_pr_blocked(tgo_ctx* ctx, int32_t world, int64_t active_span, int64_
     }
     int64_t H = env_i64("TGO_PR_HOT", pr_hot_default()) / world;
     H = std::min(active_span, std::max<int64_t>(64, H / 64 * 64));
-    if (ctx->part_pr_world == world && ctx->part_pr_hot == H && ctx->part_pr_span == active_span) {
+    // the fixed-point range is the job's: from the longest in-row of ANY rank (agreed by the
+    // driver, tgo_part_pr_set_longest_row), so what a rank with short rows emits is checked
+    // against the range of the peer that sums the longest row
+    const int64_t job_row = std::max(ctx->part_pr_job_row, ctx->part_max_in_row);
+    if (ctx->part_pr_world == world && ctx->part_pr_hot == H && ctx->part_pr_span == active_span &&
+        ctx->part_pr_built_row == job_row) {
         *hot_per_rank = H;
         return TGO_OK;                                  // already built for this layout
     }
@@ -671,7 +695,8 @@ int tgo_part_pr_blocked(tgo_ctx* ctx, int32_t world, int64_t active_span, int64_
     }
     bool ready = false;
     const std::vector<int32_t> no_host_adj;
-    if ((rc = upload_cold_blocks(ctx, off, no_host_adj, W * A, W * H, g.n_active, g.cold_in, ready, g.in.off, gidx, nnz)))
+    if ((rc = upload_cold_blocks(ctx, off, no_host_adj, W * A, W * H, g.n_active, g.cold_in, ready, g.in.off, gidx, nnz, 0,
+                                 job_row)))
         return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     g.cold_in_ready = ready;
@@ -684,6 +709,7 @@ int tgo_part_pr_blocked(tgo_ctx* ctx, int32_t world, int64_t active_span, int64_
     ctx->part_pr_world = world;
     ctx->part_pr_hot = H;
     ctx->part_pr_span = A;
+    ctx->part_pr_built_row = job_row;
     ctx->st.device_bytes = ctx->dev_bytes;
     *hot_per_rank = H;
     return TGO_OK;

@@ -50,6 +50,10 @@ struct tgo_ctx {
     int32_t part_pr_world = 0;  // blocked gathered layout (tgo_part_pr_blocked): world, H, A
     bool part_pr_plain = false; // tgo_part_pr_plain: the plain layout although the blocked one is built
     int64_t part_pr_hot = 0, part_pr_span = 0;
+    // the fixed-point range of the blocked layout is the job's (DESIGN.md FxGuard): the longest
+    // in-row of this rank, the longest of any rank as the driver agreed it (0 = not told), and
+    // the length the layout in g.cold_in was built for
+    int64_t part_max_in_row = 0, part_pr_job_row = 0, part_pr_built_row = 0;
     int64_t part_relaxed = 0;   // partitioned SSSP: entries relaxed, phases
     int32_t part_phases = 0;
     int64_t part_seed = -1;     // partitioned SSSP: the seed's internal id when owned here
@@ -279,7 +283,7 @@ int64_t pr_hot_default();
 int upload_cold_blocks(tgo_ctx* ctx, const std::vector<int64_t>& off, const std::vector<int32_t>& adj,
                        int64_t n_src, int64_t hot, int64_t n_rows, ColdBlocks& cb, bool& ready,
                        const int64_t* d_off = nullptr, const int32_t* d_adj = nullptr, int64_t d_nnz = 0,
-                       int64_t win = 0);
+                       int64_t win = 0, int64_t job_row = 0);
 int part_upload(tgo_ctx* ctx, HostGraph& h, int64_t n_global, int64_t lo);
 int part_rows_take(tgo_ctx* ctx, RowStaging& st, std::string& err);
 // a failed row load: the staged rows and the decoder's buffers go together

@@ -875,10 +875,12 @@ extern "C" int tgo_part_pagerank_run(tgo_ctx* ctx, tgo_exchange* x, const tgo_pr
     const int W = x->world, R = x->rank;
     hipStream_t st = d.st;
     // layout: active span A = max active rows (every rank), the blocked hot-first layout
-    int64_t act = 0, span = 0, hot = 0;
-    if ((rc = tgo_part_active_rows(ctx, &act))) return rc;
-    if ((rc = d.reduce(&act, 1, tgo_exchange::kRedMax, &span))) return rc;
-    if ((rc = tgo_part_pr_blocked(ctx, W, span, &hot))) return rc;
+    // and the longest in-row of any rank: the fixed-point range is one per job, not per rank
+    int64_t own[2] = {0, 0}, all[2] = {0, 0}, hot = 0;
+    if ((rc = tgo_part_active_rows(ctx, &own[0])) || (rc = tgo_part_pr_longest_row(ctx, &own[1]))) return rc;
+    if ((rc = d.reduce(own, 2, tgo_exchange::kRedMax, all))) return rc;
+    int64_t span = all[0];
+    if ((rc = tgo_part_pr_set_longest_row(ctx, all[1])) || (rc = tgo_part_pr_blocked(ctx, W, span, &hot))) return rc;
     if (hot == 0) span = nl;                     // plain layout: rank-major n_local slices
     double *contrib = nullptr, *gath = nullptr;
     if ((rc = scratch(ctx, contrib, nl, 18)) || (rc = scratch(ctx, gath, static_cast<int64_t>(W) * span, 19))) return rc;
@@ -939,6 +941,7 @@ extern "C" int tgo_part_pagerank_run(tgo_ctx* ctx, tgo_exchange* x, const tgo_pr
             hot = 0;
             span = nl;
             gh = nullptr;
+            moved = 0;                           // the discarded blocked run's traffic is not the job's
             if ((rc = scratch(ctx, gath, static_cast<int64_t>(W) * span, 19))) { tgo_part_pr_plain(ctx, 0); return rc; }
             goto rerun;
         }

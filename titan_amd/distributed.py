@@ -508,6 +508,17 @@ class HipPartBackend:
         self.e.part_call("tgo_part_active_rows", C.byref(a))
         return a.value
 
+    def pr_longest_row(self):
+        """The longest in-row of this rank's rows (tgo_part_pr_longest_row)."""
+        a = C.c_int64()
+        self.e.part_call("tgo_part_pr_longest_row", C.byref(a))
+        return a.value
+
+    def pr_set_longest_row(self, longest_row):
+        """The longest in-row of any rank, agreed before pr_layout: the blocked layout's fixed-point
+        range is the job's, not the rank's (tgo_part_pr_set_longest_row)."""
+        self.e.part_call("tgo_part_pr_set_longest_row", C.c_int64(longest_row))
+
     def pr_layout(self, world, active_span):
         """Hot rows per rank of the blocked gathered layout (tgo_part_pr_blocked); 0 = plain."""
         h = C.c_int64()
@@ -932,12 +943,19 @@ def gathered_index(u, n_local: int, world: int, hot: int, span: int):
 
 def pagerank_layout(backend, group=None, comm=None):
     """(hot rows per rank H, active span A) agreed by every rank: A = max active rows
-    (all-reduce MAX), H from the backend (0 = plain rank-major layout, A = n_local)."""
+    (all-reduce MAX), H from the backend (0 = plain rank-major layout, A = n_local).  The same
+    all-reduce agrees on the longest in-row of any rank, which sets the one range in which the
+    blocked layout's fixed-point passes are exact on every rank of the job.  A backend whose
+    sums have no such range (plain fp64 sums: no pr_longest_row) takes part in the all-reduce
+    with 0 and is told nothing, so the collective is the same whatever the backend."""
     cm = _comm(comm, group)
     world = cm.world
-    t = torch.tensor([backend.active_rows()], dtype=torch.int64, device=backend.device)
+    own_row = getattr(backend, "pr_longest_row", None)
+    t = torch.tensor([backend.active_rows(), own_row() if own_row else 0], dtype=torch.int64, device=backend.device)
     cm.all_reduce(t, op="max")
-    span = int(t.item())
+    span, longest = (int(x) for x in t.cpu())
+    if own_row:
+        backend.pr_set_longest_row(longest)
     hot = backend.pr_layout(world, span)
     return (hot, span) if hot > 0 else (0, backend.n_local)
 
