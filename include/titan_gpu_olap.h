@@ -606,6 +606,53 @@ typedef struct { int64_t clusters, largest, changed_last; int32_t rounds, conver
 int  tgo_peer_pressure(tgo_ctx* ctx, const tgo_pp_args* args, int64_t* cluster_out, tgo_pp_info* info);
 int  tgo_copy_peer_pressure(tgo_ctx* ctx, int64_t* cluster_out);
 
+/* ---- Closeness and harmonic centrality ----------------------------------------------------
+ * The distance-based centralities over the loaded scope, whichever of the three it is, folded on the
+ * device out of tgo_bfs_multi's sweeps.  d(s, v) is the distance tgo_bfs_multi gives v from seed s on
+ * this load: parallel entries, self-loops, row caps and vertex cuts behave exactly as there, and weights
+ * are ignored.  args->max_depth >= 0 is passed to the sweep unchanged: a distance above it counts as "not
+ * reached".  Per vertex v in row order, with R(v) the seeds s != v, in the order given, that reach v:
+ *   far[v]       = sum over R(v) of d(s, v)
+ *   reach[v]     = |R(v)|
+ *   ecc[v]       = max over R(v) of d(s, v); 0 when R(v) is empty
+ *   closeness[v] = (double)reach[v] / (double)far[v]: one IEEE division of integers below 2^53, so it is
+ *                  bit-exact; 0.0 when far[v] = 0
+ *   harmonic[v]  = sum over R(v) of 1 / d(s, v), folded in the order below
+ * READING: v accumulates its distances FROM the seeds — in-closeness along the direction messages flow
+ * (OUT_E: along the OUT entries); on a bothE load it is symmetric.  With every vertex a seed the values are
+ * exact, with a sample of seeds they are the usual sampled estimate.  The values are UNNORMALISED:
+ * Wasserman-Faust's reach / (n - 1) factor, a division of the harmonic sum by n - 1 and the like are left to
+ * the caller, as for tgo_betweenness.
+ * seeds: nseeds Titan ids (args->seed_is_dense: row-order indices), resolved as tgo_bfs resolves its
+ * seed; nseeds = -1 with seeds = NULL: every executed vertex in row order; nseeds = 0: all zeros.  A seed
+ * given twice counts twice; a seed that is no executed vertex contributes nothing and is not counted in
+ * info->sources.  The resolved seeds, in order, are cut into batches of 64 (the last may be partial), one
+ * sweep each.
+ * HARMONIC FOLD ORDER (the contract): h = 0; the batches in order; within a batch the distinct levels
+ * L >= 1 present at v in ascending order; for each, h = h + (double)c / (double)L, c the number of the
+ * batch's sources at level L at v, the division and the addition IEEE fp64 (round to nearest).  The order
+ * depends on the seeds and the graph alone: results are bit-identical run to run and for every
+ * TGO_TUNE_MS_* value, and a host reference that folds in this order matches bit for bit.  Against the
+ * exact sum the value is within S 2^-52 relative (S seeds, every term positive).  info:
+ *   sources        seeds run
+ *   reached_pairs  sum of reach; deterministic
+ *   batches        sweeps run; also tgo_stats.iterations
+ *   max_depth      max of ecc; deterministic; also tgo_stats.levels
+ * args->scope must be the loaded scope, args->flags 0, args->max_depth >= 0, nseeds >= -1, seeds non-NULL
+ * when nseeds > 0 (else TGO_E_INVALID).  A partitioned ctx, and a level above 65534 (the sweep's own limit;
+ * its message is passed on): TGO_E_UNSUPPORTED.  A failed call leaves the ctx usable.  closeness_out /
+ * harmonic_out may each be NULL: the result stays on the device either way (tgo_copy_closeness, every
+ * array of which may be NULL; tgo_result_rows kind TGO_RESULT_CLOSENESS).  tgo_copy_closeness after
+ * another program: TGO_E_STATE.  The sweep's state afterwards is the last batch's:
+ * tgo_copy_multi_distances(source r) returns the distances from the r-th seed of the last batch.  The
+ * accumulators (36 bytes per vertex) are allocated by the first run (tgo_stats.device_bytes). */
+typedef struct { int32_t scope; int32_t flags; int32_t max_depth; int32_t seed_is_dense; } tgo_cl_args;
+typedef struct { int64_t sources, reached_pairs; int32_t batches, max_depth; } tgo_cl_info;
+int  tgo_closeness(tgo_ctx* ctx, const tgo_cl_args* args, const int64_t* seeds, int64_t nseeds,
+                   double* closeness_out, double* harmonic_out, tgo_cl_info* info);
+int  tgo_copy_closeness(tgo_ctx* ctx, int64_t* far_out, int64_t* reach_out, int64_t* ecc_out,
+                        double* closeness_out, double* harmonic_out);   /* each may be NULL */
+
 /* ---- Generic vertex programs ----------------------------------------
  * A vertex program the engine does not implement natively runs its execute() on the host
  * over whole per-vertex vectors (titan_amd/computer.py GenericVertexProgram; the Java host
@@ -718,6 +765,9 @@ int  tgo_dense_ids(tgo_ctx* ctx, const int64_t* titan_ids, int64_t count, int64_
  *   BETWEENNESS  tgo_betweenness's value (Double) on every executed vertex, encoded exactly as
  *             PAGE_RANK; any other typed key: TGO_E_INVALID
  *   PEER_PRESSURE  tgo_peer_pressure's cluster, encoded exactly as COMPONENT
+ *   CLOSENESS tgo_closeness's closeness (key_ids[0]) and harmonic centrality (key_ids[1]), two Doubles on
+ *             every executed vertex, encoded exactly as PAGERANK's pair; any other typed key:
+ *             TGO_E_INVALID
  * Compute keys are typed property keys of those datatypes, or generic keys (TGO_DT_OBJECT: what
  * getOrCreatePropertyKey makes for a key the program sets without a schema, DefaultSchemaMaker
  * .java:46-48), whose values carry their class (Long 13, Double 20, Integer 12).  Relation ids are
@@ -728,11 +778,11 @@ int  tgo_dense_ids(tgo_ctx* ctx, const int64_t* titan_ids, int64_t count, int64_
 typedef enum { TGO_RESULT_DISTANCE = 0, TGO_RESULT_PAGERANK = 1, TGO_RESULT_DEGREE = 2,
                TGO_RESULT_VALUES = 3, TGO_RESULT_COMPONENT = 4, TGO_RESULT_TRIANGLES = 5,
                TGO_RESULT_CORE = 6, TGO_RESULT_SCC = 7, TGO_RESULT_BETWEENNESS = 8,
-               TGO_RESULT_PEER_PRESSURE = 9 } tgo_result_kind;
+               TGO_RESULT_PEER_PRESSURE = 9, TGO_RESULT_CLOSENESS = 10 } tgo_result_kind;
 typedef struct {
     int32_t kind;                 /* tgo_result_kind                                          */
     int32_t reserved;             /* TGO_RESULT_VALUES: tgo_value_type of the values           */
-    int64_t key_ids[2];           /* [0] DISTANCE / PAGE_RANK / DEGREE / COMPONENT / TRIANGLES / CORE / SCC / BETWEENNESS / PEER_PRESSURE key; [1] OUTGOING_EDGE_COUNT / CLUSTERING */
+    int64_t key_ids[2];           /* [0] DISTANCE / PAGE_RANK / DEGREE / COMPONENT / TRIANGLES / CORE / SCC / BETWEENNESS / PEER_PRESSURE / CLOSENESS key; [1] OUTGOING_EDGE_COUNT / CLUSTERING / HARMONIC */
     int32_t datatypes[2];         /* tgo_datatype of each key                                  */
     int64_t relation_id_base;
 } tgo_result_args;

@@ -378,6 +378,43 @@ JNIEXPORT jlongArray JNICALL JFN(peerPressure)(JNIEnv* env, jclass cls, jlong h,
     return distances(env, h, run_peer_pressure, &a);
 }
 
+/* tgo_closeness over the loaded scope: {double[] closeness, double[] harmonic} in row order, accumulated
+ * from the seeds (Titan ids, 64 a sweep; a null array: every vertex), unnormalised; max_depth >= 0: a
+ * distance above it counts as not reached.  NULL on error (the sweeps run are tgo_stats.iterations
+ * afterwards; write-back: tgo_result_rows kind TGO_RESULT_CLOSENESS). */
+JNIEXPORT jobjectArray JNICALL JFN(closeness)(JNIEnv* env, jclass cls, jlong h, jlongArray seeds, jint scope, jint max_depth) {
+    (void)cls;
+    if (!fits_jsize(env, tgo_num_vertices(CTX(h)), "more vertices than a Java array holds")) return NULL;
+    jsize n = (jsize)tgo_num_vertices(CTX(h));
+    jdoubleArray cl = (*env)->NewDoubleArray(env, n);
+    jdoubleArray ha = (*env)->NewDoubleArray(env, n);
+    jclass dcls = (*env)->FindClass(env, "[D");
+    jobjectArray out = dcls ? (*env)->NewObjectArray(env, 2, dcls, NULL) : NULL;
+    if (!cl || !ha || !out) return NULL;
+    tgo_cl_args a;
+    memset(&a, 0, sizeof a);
+    a.scope = scope;
+    a.max_depth = max_depth;
+    jlong* s = NULL;
+    int64_t nseeds = -1;
+    if (seeds) {
+        nseeds = (*env)->GetArrayLength(env, seeds);
+        s = (*env)->GetLongArrayElements(env, seeds, NULL);
+        if (!s) return NULL;
+    }
+    jdouble* pc = (*env)->GetDoubleArrayElements(env, cl, NULL);
+    jdouble* ph = (*env)->GetDoubleArrayElements(env, ha, NULL);
+    int rc = pc && ph ? tgo_closeness(CTX(h), &a, nseeds > 0 ? (const int64_t*)s : NULL, nseeds, (double*)pc, (double*)ph, NULL)
+                      : TGO_E_OOM;
+    if (pc) (*env)->ReleaseDoubleArrayElements(env, cl, pc, 0);
+    if (ph) (*env)->ReleaseDoubleArrayElements(env, ha, ph, 0);
+    if (s) (*env)->ReleaseLongArrayElements(env, seeds, s, JNI_ABORT);
+    if (rc != TGO_OK) return NULL;
+    (*env)->SetObjectArrayElement(env, out, 0, cl);
+    (*env)->SetObjectArrayElement(env, out, 1, ha);
+    return out;
+}
+
 /* tgo_result_rows: Object[5] = {long[] rowKeys, long[] rowEntryBegin, long[] rowByteBegin,
  * long[] entryLimitValuePos, byte[] entryBytes}, or NULL on error (status: lastError; a result
  * beyond the int32 index range of a Java array: IllegalStateException). */

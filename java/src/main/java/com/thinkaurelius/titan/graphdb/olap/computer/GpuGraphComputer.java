@@ -49,7 +49,8 @@ import java.util.concurrent.Future;
  * a KCoreVertexProgram (core numbers of the same projection, tgo_kcore),
  * a StronglyConnectedComponentsVertexProgram (bothE read as a directed graph, tgo_scc),
  * a BetweennessCentralityVertexProgram (Brandes' betweenness over either reading, tgo_betweenness),
- * TinkerPop's PeerPressureVertexProgram (one vote per edge, exact integer tallies, tgo_peer_pressure).
+ * TinkerPop's PeerPressureVertexProgram (one vote per edge, exact integer tallies, tgo_peer_pressure),
+ * a ClosenessCentralityVertexProgram (closeness and harmonic centrality out of 64-source sweeps, tgo_closeness).
  *
  * Write-back (FulgoraGraphComputer.java:248-305): with Persist.VERTEX_PROPERTIES the compute
  * keys are encoded on the device (tgo_result_rows: single-cardinality property entries, one
@@ -553,8 +554,30 @@ public class GpuGraphComputer implements TitanGraphComputer {
                 case "org.apache.tinkerpop.gremlin.process.computer.clustering.peerpressure.PeerPressureVertexProgram":
                     return new PeerPressure(voteScopeOf(conf), conf.getBoolean("gremlin.peerPressureVertexProgram.distributeVote", false),
                             conf.getInt("gremlin.peerPressureVertexProgram.maxIterations", 30));
+                case "com.thinkaurelius.titan.olap.ClosenessCentralityVertexProgram":
+                    return new Closeness(closenessSeedsOf(conf), closenessScopeOf(conf),
+                            conf.getInt("titan.closeness.maxDepth", Integer.MAX_VALUE));
                 default:
                     throw new TitanException("vertex program " + p.getClass().getName() + " is not supported on the GPU path");
+            }
+        }
+
+        /** titan.closeness.seeds: the Titan ids the sums run over, in order; absent: every vertex (null). */
+        private static long[] closenessSeedsOf(BaseConfiguration conf) {
+            if (!conf.containsKey("titan.closeness.seeds")) return null;
+            java.util.List<?> l = conf.getList("titan.closeness.seeds");
+            long[] s = new long[l.size()];
+            for (int i = 0; i < s.length; i++) s[i] = Long.parseLong(l.get(i).toString());
+            return s;
+        }
+
+        /** titan.closeness.edges: the edges the distances run along (outE, inE, bothE); absent: bothE. */
+        private static int closenessScopeOf(BaseConfiguration conf) {
+            switch (conf.getString("titan.closeness.edges", "bothE")) {
+                case "outE": return TgoNative.SCOPE_OUT_E;
+                case "inE": return TgoNative.SCOPE_IN_E;
+                case "bothE": return TgoNative.SCOPE_BOTH_E;
+                default: throw new TitanException("titan.closeness.edges must be outE, inE or bothE");
             }
         }
 
@@ -853,6 +876,37 @@ public class GpuGraphComputer implements TitanGraphComputer {
         }
         void emit(long[] ids, Map<String, Object> values, FulgoraMapEmitter emitter) {
             long[] c = (long[]) values.get(CLUSTER);
+            for (int i = 0; i < ids.length; i++) emitter.emit(ids[i], c[i]);
+        }
+    }
+
+    /**
+     * Closeness and harmonic centrality (tgo_closeness): per vertex, over the seeds other than itself that
+     * reach it, CLOSENESS = their number / the sum of their distances and HARMONIC = the sum of
+     * 1 / distance; in-closeness along the message flow, unnormalised.  The iteration reported is the
+     * number of 64-source sweeps run, known after run().
+     */
+    static final class Closeness extends DeviceProgram {
+        static final String CLOSENESS = "titan.closeness.closeness";
+        static final String HARMONIC = "titan.closeness.harmonic";
+        final long[] seeds; final int scope; final int maxDepth;
+        private int batches;
+        Closeness(long[] seeds, int scope, int maxDepth) { this.seeds = seeds; this.scope = scope; this.maxDepth = maxDepth; }
+        int scope() { return scope; }
+        int iterations() { return batches; }
+        int resultKind() { return TgoNative.RESULT_CLOSENESS; }
+        String[] computeKeys() { return new String[]{CLOSENESS, HARMONIC}; }
+        int[] computeKeyTypes() { return new int[]{TgoNative.DT_DOUBLE, TgoNative.DT_DOUBLE}; }
+        Map<String, Object> run(long ctx) {
+            Map<String, Object> v = new HashMap<>();
+            double[][] r = TgoNative.checked(ctx, TgoNative.closeness(ctx, seeds, scope, maxDepth));
+            v.put(CLOSENESS, r[0]);
+            v.put(HARMONIC, r[1]);
+            batches = (int) TgoNative.stats(ctx)[3];
+            return v;
+        }
+        void emit(long[] ids, Map<String, Object> values, FulgoraMapEmitter emitter) {
+            double[] c = (double[]) values.get(CLOSENESS);
             for (int i = 0; i < ids.length; i++) emitter.emit(ids[i], c[i]);
         }
     }

@@ -118,13 +118,23 @@ public final class TgoNative {
      */
     public static native long[] peerPressure(long ctx, int voteScope, boolean distribute, int maxRounds);
 
+    /**
+     * tgo_closeness over the loaded scope (scope must name it): {closeness, harmonic} per vertex in row
+     * order, accumulated from the seeds (Titan ids, in that order, 64 a sweep; null: every vertex):
+     * closeness = the seeds that reach the vertex / the sum of their distances (0.0 when none does),
+     * harmonic = the sum of 1 / distance in the engine's fixed fold order.  In-closeness along the message
+     * flow, unnormalised.  maxDepth >= 0: a distance above it counts as not reached (Integer.MAX_VALUE: no
+     * cut).  null on failure.  stats()[3] then holds the sweeps run.
+     */
+    public static native double[][] closeness(long ctx, long[] seeds, int scope, int maxDepth);
+
     /** tgo_stats_get: {ghostVertices, truncatedResults, skippedRows, iterations, loadMs, lastKernelMs}. */
     public static native double[] stats(long ctx);
 
     /** tgo_result_kind */
     public static final int RESULT_DISTANCE = 0, RESULT_PAGERANK = 1, RESULT_DEGREE = 2, RESULT_COMPONENT = 4,
             RESULT_TRIANGLES = 5, RESULT_CORE = 6, RESULT_SCC = 7, RESULT_BETWEENNESS = 8,
-            RESULT_PEER_PRESSURE = 9;
+            RESULT_PEER_PRESSURE = 9, RESULT_CLOSENESS = 10;
     /**
      * tgo_result_rows: the edgestore entries (single-cardinality property entries) of the last
      * program's compute keys, as {long[] rowKeys, long[] rowEntryBegin, long[] rowByteBegin,

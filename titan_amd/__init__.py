@@ -7,6 +7,7 @@ TitanGraphComputer API plus a thin ctypes binding; it has no CPU fallback.
 from .engine import Engine, Rows, Schema, TitanException, rmat_edges, pick_roots, synth_rows  # noqa: F401
 from .computer import (  # noqa: F401
     BetweennessCentralityVertexProgram, BetweennessRankMapReduce,
+    ClosenessCentralityVertexProgram, ClosenessRankMapReduce,
     ClusterCountMapReduce, ClusterPopulationMapReduce, ConnectedComponentVertexProgram, CoreSizeMapReduce,
     DegeneracyMapReduce, DegreeCounter, DegreeMapper, ExecutionException, GpuGraph, GpuGraphComputer,
     KCoreVertexProgram, KeyValue, PeerPressureVertexProgram,
@@ -31,5 +32,6 @@ __all__ = [
     "KCoreVertexProgram", "DegeneracyMapReduce", "CoreSizeMapReduce",
     "StronglyConnectedComponentsVertexProgram", "SccSizeMapReduce",
     "BetweennessCentralityVertexProgram", "BetweennessRankMapReduce",
+    "ClosenessCentralityVertexProgram", "ClosenessRankMapReduce",
     "PeerPressureVertexProgram",
 ]

@@ -37,6 +37,7 @@ RESULT_CORE = 6
 RESULT_SCC = 7
 RESULT_BETWEENNESS = 8
 RESULT_PEER_PRESSURE = 9
+RESULT_CLOSENESS = 10
 CC_HOOK, CC_PROPAGATE = 0, 1     # tgo_cc_path
 SSSP_HOP_BOUNDED, SSSP_DELTA = 0, 1
 FLAG_STATS = 1
@@ -197,6 +198,14 @@ class PpInfo(C.Structure):
                 ("rounds", C.c_int32), ("converged", C.c_int32)]
 
 
+class ClArgs(C.Structure):
+    _fields_ = [("scope", C.c_int32), ("flags", C.c_int32), ("max_depth", C.c_int32), ("seed_is_dense", C.c_int32)]
+
+
+class ClInfo(C.Structure):
+    _fields_ = [("sources", C.c_int64), ("reached_pairs", C.c_int64), ("batches", C.c_int32), ("max_depth", C.c_int32)]
+
+
 class GatherArgs(C.Structure):
     _fields_ = [("scope", C.c_int32), ("value_type", C.c_int32), ("combiner", C.c_int32), ("edge_fn", C.c_int32)]
 
@@ -227,7 +236,7 @@ EXPORTS = [
     "tgo_gather_lists", "tgo_result_rows_values", "tgo_set_edge_program",
     "tgo_components", "tgo_copy_components", "tgo_triangles", "tgo_copy_triangles",
     "tgo_kcore", "tgo_copy_cores", "tgo_scc", "tgo_copy_scc", "tgo_betweenness", "tgo_copy_betweenness",
-    "tgo_peer_pressure", "tgo_copy_peer_pressure",
+    "tgo_peer_pressure", "tgo_copy_peer_pressure", "tgo_closeness", "tgo_copy_closeness",
     "tgo_rmat_edges", "tgo_rmat_edges_device", "tgo_rmat_partition_device", "tgo_pick_roots", "tgo_synth_rows",
     # titan_gpu_olap_part.h (1-D vertex-partitioned multi-GPU)
     "tgo_load_partition", "tgo_part_layout", "tgo_load_partition_layout", "tgo_part_bfs_begin", "tgo_part_bfs_td", "tgo_part_bfs_claim", "tgo_part_bfs_bu",
@@ -296,6 +305,9 @@ def load() -> C.CDLL:
         "tgo_copy_betweenness": (C.c_int, [vp, C.POINTER(C.c_double)]),
         "tgo_peer_pressure": (C.c_int, [vp, P(PpArgs), _i64p, P(PpInfo)]),
         "tgo_copy_peer_pressure": (C.c_int, [vp, _i64p]),
+        "tgo_closeness": (C.c_int, [vp, P(ClArgs), _i64p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                    P(ClInfo)]),
+        "tgo_copy_closeness": (C.c_int, [vp, _i64p, _i64p, _i64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "tgo_pagerank": (C.c_int, [vp, P(PrArgs), C.POINTER(C.c_double)]),
         "tgo_walkcount": (C.c_int, [vp, C.c_int32, _i32p]),
         "tgo_stats_get": (C.c_int, [vp, P(Stats)]),

@@ -477,6 +477,55 @@ class BetweennessCentralityVertexProgram(VertexProgram):
         return BetweennessCentralityVertexProgram.Builder()
 
 
+class ClosenessCentralityVertexProgram(VertexProgram):
+    """Closeness and harmonic centrality (tgo_closeness) over the edges named by edges(scope_name)
+    ("bothE" by default; "outE" / "inE": distances along that direction of message flow).  Per vertex,
+    over the seeds s other than the vertex that reach it: CLOSENESS = their number / the sum of their
+    distances (Double; 0.0 when none reaches it), HARMONIC = the sum of 1 / distance (Double), folded in
+    the engine's contractual order.  Both are unnormalised in-closeness from the seeds.  seeds(ids): the
+    Titan ids the sums run over, in that order, 64 a sweep; without it every vertex (exact values).
+    maxDepth(d): a distance above d counts as not reached.  memory.getIteration() reports the sweeps
+    run.  Result graph and persist preference as ShortestDistanceVertexProgram."""
+    CLOSENESS = "titan.closeness.closeness"
+    HARMONIC = "titan.closeness.harmonic"
+    compute_keys = (CLOSENESS, HARMONIC)
+    scope_name = "bothE"
+
+    def __init__(self, seeds=None, max_depth=None, edges="bothE"):
+        if edges not in SCOPE_NAMES:
+            raise TitanException(L.TGO_E_INVALID, f"unknown edge scope {edges!r}")
+        if max_depth is not None and not 0 <= int(max_depth) <= 2**31 - 1:
+            raise TitanException(L.TGO_E_INVALID, "maxDepth must be in [0, 2^31 - 1]")
+        self.seeds = None if seeds is None else [int(s) for s in seeds]
+        self.max_depth = None if max_depth is None else int(max_depth)
+        self.scope_name = edges
+
+    class Builder:
+        def __init__(self):
+            self._seeds = None
+            self._max_depth = None
+            self._edges = "bothE"
+
+        def seeds(self, ids):
+            self._seeds = [int(s) for s in ids]
+            return self
+
+        def maxDepth(self, d):  # noqa: N802
+            self._max_depth = d
+            return self
+
+        def edges(self, scope_name):
+            self._edges = scope_name
+            return self
+
+        def create(self, graph=None):
+            return ClosenessCentralityVertexProgram(self._seeds, self._max_depth, self._edges)
+
+    @staticmethod
+    def build():
+        return ClosenessCentralityVertexProgram.Builder()
+
+
 class PeerPressureVertexProgram(VertexProgram):
     """TinkerPop's PeerPressureVertexProgram over bothE (tgo_peer_pressure): every edge carries one
     vote, parallel edges and self-loops included.  CLUSTER = the Titan id of the vertex's cluster
@@ -770,6 +819,53 @@ class BetweennessRankMapReduce(MapReduce):
         return [KeyValue(int(ids[i]), float(bc[i])) for i in order]
 
 
+class ClosenessRankMapReduce(MapReduce):
+    """The `top` vertices of largest closeness (or, with by(HARMONIC), harmonic centrality) as
+    (Titan id, value) pairs, largest first, ties broken by the smaller id."""
+    DEFAULT_MEMORY_KEY = "closenessRank"
+
+    def __init__(self, key=DEFAULT_MEMORY_KEY, top=10, by=ClosenessCentralityVertexProgram.CLOSENESS):
+        if by not in ClosenessCentralityVertexProgram.compute_keys:
+            raise TitanException(L.TGO_E_INVALID, f"ClosenessRankMapReduce ranks by CLOSENESS or HARMONIC, not {by!r}")
+        self.memory_key = key
+        self.top = int(top)
+        self.by = by
+
+    class Builder:
+        def __init__(self):
+            self._k = ClosenessRankMapReduce.DEFAULT_MEMORY_KEY
+            self._top = 10
+            self._by = ClosenessCentralityVertexProgram.CLOSENESS
+
+        def memoryKey(self, k):  # noqa: N802
+            self._k = k
+            return self
+
+        def top(self, k):
+            self._top = int(k)
+            return self
+
+        def by(self, compute_key):
+            self._by = compute_key
+            return self
+
+        def create(self):
+            return ClosenessRankMapReduce(self._k, self._top, self._by)
+
+    @staticmethod
+    def build():
+        return ClosenessRankMapReduce.Builder()
+
+    def emit(self, ids, props):
+        val = props.get(self.by)
+        if val is None:
+            return []
+        ids = np.asarray(ids, dtype=np.int64)
+        val = np.asarray(val, dtype=np.float64)
+        order = np.lexsort((ids, -val))[:max(self.top, 0)]
+        return [KeyValue(int(ids[i]), float(val[i])) for i in order]
+
+
 class DegreeMapper(MapReduce):
     DEGREE_RESULT = "degrees"                 # OLAPTest.java:420
     memory_key = DEGREE_RESULT
@@ -900,7 +996,9 @@ class GpuGraphComputer(TitanGraphComputer):
                                                                (StronglyConnectedComponentsVertexProgram.COMPONENT,)),
                     BetweennessCentralityVertexProgram: (L.RESULT_BETWEENNESS,
                                                          (BetweennessCentralityVertexProgram.CENTRALITY,)),
-                    PeerPressureVertexProgram: (L.RESULT_PEER_PRESSURE, (PeerPressureVertexProgram.CLUSTER,))}
+                    PeerPressureVertexProgram: (L.RESULT_PEER_PRESSURE, (PeerPressureVertexProgram.CLUSTER,)),
+                    ClosenessCentralityVertexProgram: (L.RESULT_CLOSENESS, (ClosenessCentralityVertexProgram.CLOSENESS,
+                                                                            ClosenessCentralityVertexProgram.HARMONIC))}
 
     def _result_mode(self):
         """resultMode if set, else the program's preferred (ResultGraph, Persist) as Fulgora
@@ -1023,6 +1121,14 @@ class GpuGraphComputer(TitanGraphComputer):
             props[PeerPressureVertexProgram.CLUSTER], info = eng.peer_pressure(
                 SCOPE_NAMES[p.edges], distribute=p.distribute, max_rounds=p.max_iterations)
             iteration = info["rounds"]
+            ids = eng.vertex_ids()
+        elif isinstance(p, ClosenessCentralityVertexProgram):
+            scope = SCOPE_NAMES[p.scope_name]
+            eng = self.graph.engine_for(scope)
+            res, info = eng.closeness(p.seeds, max_depth=p.max_depth, scope=scope)
+            props[ClosenessCentralityVertexProgram.CLOSENESS] = res["closeness"]
+            props[ClosenessCentralityVertexProgram.HARMONIC] = res["harmonic"]
+            iteration = info["batches"]
             ids = eng.vertex_ids()
         else:
             raise TitanException(L.TGO_E_UNSUPPORTED, f"vertex program {type(p).__name__} is not supported on the GPU path")

@@ -279,7 +279,7 @@ static int result_rows_impl(tgo_ctx* ctx, const tgo_result_args* a, const Result
 int tgo_result_rows(tgo_ctx* ctx, const tgo_result_args* a, tgo_result_size* size, const tgo_rows_buf* out) {
     if (!ctx) return TGO_E_INVALID;
     if (!a || !size) return fail(ctx, TGO_E_INVALID, "null args");
-    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_PEER_PRESSURE || a->kind == TGO_RESULT_VALUES)
+    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_CLOSENESS || a->kind == TGO_RESULT_VALUES)
         return fail(ctx, TGO_E_INVALID, "invalid result kind");
     if (ctx->res_kind != a->kind)
         return fail(ctx, TGO_E_STATE, "no finished program of that kind is the last one run on this ctx");
@@ -300,6 +300,10 @@ int tgo_result_rows(tgo_ctx* ctx, const tgo_result_args* a, tgo_result_size* siz
         return fail(ctx, TGO_E_INVALID, "the component label's compute key must be Long, Integer or generic (Object)");
     if (a->kind == TGO_RESULT_BETWEENNESS && a->datatypes[0] != TGO_DT_DOUBLE && a->datatypes[0] != TGO_DT_OBJECT)
         return fail(ctx, TGO_E_INVALID, "the betweenness value's compute key must be Double or generic (Object)");
+    if (a->kind == TGO_RESULT_CLOSENESS)
+        for (int k = 0; k < 2; ++k)
+            if (a->datatypes[k] != TGO_DT_DOUBLE && a->datatypes[k] != TGO_DT_OBJECT)
+                return fail(ctx, TGO_E_INVALID, "the closeness and harmonic compute keys must be Double or generic (Object)");
     return result_rows_impl(ctx, a, ctx->res_src, ctx->res_empty, size, out);
 }
 

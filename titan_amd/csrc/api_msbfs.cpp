@@ -84,34 +84,25 @@ static int ms_cold_layout(tgo_ctx* ctx, int32_t scope, const View& pull, int64_t
     return TGO_OK;
 }
 
-extern "C" {
+namespace tgo {
 
-int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_bfs_args* a, int64_t* dist_out) {
-    if (!ctx) return TGO_E_INVALID;
-    ctx->res_kind = -1;
-    if (!a || !seeds) return fail(ctx, TGO_E_INVALID, "null args");
-    if (nseeds < 1 || nseeds > TGO_MAX_SOURCES) return fail(ctx, TGO_E_INVALID, "nseeds must be in [1, 64]");
-    int rc = check_program(ctx, a->scope);
-    if (rc) return rc;
-    if (a->max_depth < 0) return fail(ctx, TGO_E_INVALID, "max_depth < 0");
-    (void)hipSetDevice(ctx->opts.device);
-    if ((rc = ms_alloc(ctx))) return rc;
+// One sweep of up to 64 sources: `in` holds the sources as internal ids (all >= 0; one given twice
+// takes two bits).  On return sc.ms_vis holds the reached-by masks, sc.ms_lvl the level planes
+// [0, sc.ms_nplanes), sc.ms_nsrc = nseeds; tgo_stats.levels = the levels run.
+int run_ms_sweep(tgo_ctx* ctx, const int64_t* in, int32_t nseeds, int32_t max_depth, int32_t scope, int32_t flags) {
+    int rc = TGO_OK;
     DevGraph& g = ctx->g;
     Scratch& s = ctx->sc;
     hipStream_t st = ctx->stream;
     const int64_t n = g.n;
-    const View pull = pull_view(g, a->scope), push = push_view(g, a->scope);
-    std::vector<int64_t> in(nseeds);
+    const View pull = pull_view(g, scope), push = push_view(g, scope);
     std::vector<int32_t> uniq;
-    for (int r = 0; r < nseeds; ++r) {
-        if ((rc = resolve_seed(ctx, seeds[r], a->seed_is_dense, in[r]))) return rc;
-        if (in[r] < 0) return fail(ctx, TGO_E_INVALID, "multi-source BFS needs seeds that are executed vertices");
+    for (int r = 0; r < nseeds; ++r)
         if (std::find(uniq.begin(), uniq.end(), static_cast<int32_t>(in[r])) == uniq.end())
             uniq.push_back(static_cast<int32_t>(in[r]));
-    }
     s.ms_nsrc = nseeds;
     HIP_TRY(hipEventRecord(ctx->ev0, st));
-    HIP_TRY(hipMemcpyAsync(s.ms_seeds, in.data(), nseeds * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s.ms_seeds, in, nseeds * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(s.q[0], uniq.data(), uniq.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(s.ms_vis, 0, n * 8, st));
     // both mask buffers are still zero when the last sweep ended on an empty sparse level; the
@@ -123,7 +114,7 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
     HIP_TRY(k_ms_seed(s.ms_seeds, nseeds, s.ms_vis, s.ms_fr, INT64_MAX, st));
     HIP_TRY(k_degree_i64(push, s.q[0], static_cast<int64_t>(uniq.size()), s.qdeg, st));
     const uint64_t full = nseeds == 64 ? ~0ULL : ((1ULL << nseeds) - 1ULL);
-    const int64_t total = pull.nlists > 1 ? g.out.nnz + g.in.nnz : (a->scope == TGO_SCOPE_IN_E ? g.out.nnz : g.in.nnz);
+    const int64_t total = pull.nlists > 1 ? g.out.nnz + g.in.nnz : (scope == TGO_SCOPE_IN_E ? g.out.nnz : g.in.nnz);
     static const double ms_alpha = env_double("TGO_MS_ALPHA", 12.0);
     static const bool trace = trace_on();
     // frontier-bitmap filter of pull levels: measured slower (every pull level: 3.07 -> 3.99 ms,
@@ -160,7 +151,7 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
     // measured slower at RMAT-24 (second level 446 -> 561 us, profiles/r04t_ms_push_ab.log): off
     static const int push_range_log2 = static_cast<int>(env_double("TGO_MS_PUSH_RANGE", 0.0));
     static const int64_t push_range_min = static_cast<int64_t>(env_double("TGO_MS_PUSH_RANGE_MIN", 1048576.0));
-    const int depth = std::min(a->max_depth, 65534);
+    const int depth = std::min(max_depth, 65534);
     uint64_t* fr = s.ms_fr;
     uint64_t* nx = s.ms_nx;
     int cur = 0, levels = 0;
@@ -270,7 +261,7 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
             static const bool cold_env = env_double("TGO_MS_COLD", 0.0) != 0.0;
             const bool cold_on = tuned_on(ctx->ms_cold, cold_env);
             if (cold_on && !prev_pull && !filter) {
-                if ((rc = ms_cold_layout(ctx, a->scope, pull, ctx->ms_cold))) return rc;
+                if ((rc = ms_cold_layout(ctx, scope, pull, ctx->ms_cold))) return rc;
                 if (g.msc_C > 0) {
                     cs.hot_lim = g.msc_hot;
                     cs.acc = s.ms_cacc;
@@ -395,21 +386,47 @@ int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_
         cur ^= 1;
         ++levels;
     }
-    if (qlen > 0 && a->max_depth > depth)
+    if (qlen > 0 && max_depth > depth)
         return fail(ctx, TGO_E_UNSUPPORTED, "multi-source BFS stores levels as uint16: depth > 65534");
-    if (int rc = program_end(ctx, a->max_depth)) return rc;
+    if (int rc = program_end(ctx, max_depth)) return rc;
     ctx->st.levels = levels;
     // the last level was sparse and found nothing: its frontier's masks are cleared, nothing was
     // written to the other buffer; ms_fr's entry-less tail (seeds only) was cleared at level 0
     s.ms_masks_zero = level0_sparse && last_sparse && qlen == 0;
-    if (a->flags & TGO_FLAG_STATS) {
+    if (flags & TGO_FLAG_STATS) {
         HIP_TRY(hipMemsetAsync(s.ms_stat, 0, 2 * TGO_MAX_SOURCES * sizeof(unsigned long long), st));
         HIP_TRY(k_ms_reach(pull, s.ms_vis, n, nseeds, s.ms_stat, s.ms_stat + TGO_MAX_SOURCES, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
+    return TGO_OK;
+}
+
+}  // namespace tgo
+
+extern "C" {
+
+int tgo_bfs_multi(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, const tgo_bfs_args* a, int64_t* dist_out) {
+    if (!ctx) return TGO_E_INVALID;
+    ctx->res_kind = -1;
+    if (!a || !seeds) return fail(ctx, TGO_E_INVALID, "null args");
+    if (nseeds < 1 || nseeds > TGO_MAX_SOURCES) return fail(ctx, TGO_E_INVALID, "nseeds must be in [1, 64]");
+    int rc = check_program(ctx, a->scope);
+    if (rc) return rc;
+    if (a->max_depth < 0) return fail(ctx, TGO_E_INVALID, "max_depth < 0");
+    (void)hipSetDevice(ctx->opts.device);
+    if ((rc = ms_alloc(ctx))) return rc;
+    std::vector<int64_t> in(nseeds);
+    for (int r = 0; r < nseeds; ++r) {
+        if ((rc = resolve_seed(ctx, seeds[r], a->seed_is_dense, in[r]))) return rc;
+        if (in[r] < 0) return fail(ctx, TGO_E_INVALID, "multi-source BFS needs seeds that are executed vertices");
+    }
+    if ((rc = run_ms_sweep(ctx, in.data(), nseeds, a->max_depth, a->scope, a->flags))) return rc;
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    const int64_t n = ctx->g.n;
     if (dist_out)
         for (int r = 0; r < nseeds; ++r) {
-            HIP_TRY(k_ms_extract(ms_planes(ctx), s.ms_nplanes, s.ms_vis, g.perm, r, s.msg, n, st));
+            HIP_TRY(k_ms_extract(ms_planes(ctx), s.ms_nplanes, s.ms_vis, ctx->g.perm, r, s.msg, n, st));
             HIP_TRY(hipMemcpyAsync(dist_out + static_cast<int64_t>(r) * n, s.msg, n * sizeof(int64_t),
                                    hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));

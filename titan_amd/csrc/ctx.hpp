@@ -305,6 +305,11 @@ double ms_split_of(const tgo_ctx* ctx);
 double ms_stay_of(const tgo_ctx* ctx);
 double ms_sparse_of(const tgo_ctx* ctx);
 int64_t ms_head_of(const tgo_ctx* ctx);
+// One sweep of up to 64 sources given as internal ids (all >= 0; ms_alloc done): the level loop of
+// tgo_bfs_multi between its seed resolution and its extraction.  Leaves sc.ms_vis, the level planes
+// [0, sc.ms_nplanes) and sc.ms_nsrc; tgo_stats as tgo_bfs_multi reports them.  tgo_bfs_multi and
+// tgo_closeness (api_analytics.cpp) run it.
+int run_ms_sweep(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, int32_t max_depth, int32_t scope, int32_t flags);
 
 inline LevelPlanes ms_planes(tgo_ctx* ctx) { return LevelPlanes{ctx->sc.ms_lvl, ctx->g.n}; }
 

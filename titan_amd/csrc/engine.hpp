@@ -625,6 +625,12 @@ struct Scratch {
     int64_t* ms_seeds = nullptr;    // 64
     unsigned long long* ms_stat = nullptr;   // 128: reached[64], entries[64]
     int32_t ms_nsrc = 0;
+    // closeness / harmonic centrality (tgo_closeness; allocated on first use), internal order
+    unsigned long long* cl_far = nullptr;     // n: sum of the distances from the seeds
+    unsigned long long* cl_reach = nullptr;   // n: seeds that reach the vertex
+    int32_t* cl_ecc = nullptr;                // n: the largest of those distances
+    double* cl_harm = nullptr;                // n: the harmonic fold
+    double* cl_close = nullptr;               // n: reach / far (the finish kernel)
     int* pk_ovf = nullptr;          // fixed-capacity exchange overflow flag (checked at ms_end)
     uint8_t* pk_touch = nullptr;    // per pack chunk: written by this level's push (PackTouch)
     int64_t* pk_cnt = nullptr;      // partitioned sparse exchange: per-chunk pair counts
@@ -1058,6 +1064,16 @@ hipError_t k_pp_init(const PpRun& r, const View& send, const int32_t* rank, void
 hipError_t k_pp_round(const PpRun& r, bool first, int tier, const void* cur, void* next, Counters* cnt, hipStream_t s);
 hipError_t k_pp_finish(const PpRun& r, const void* cur, const int32_t* inv, const int64_t* tid, int64_t* label, int32_t* hist,
                        Counters* cnt, hipStream_t s);
+
+// Closeness and harmonic centrality (cl.hip).  k_cl_fold: one finished sweep (vis, the planes [0, nplanes))
+// folded into the accumulators, one lane per internal vertex; harm continues its contractual fold.
+// k_cl_finish: close = reach / far (0.0 when far = 0); *pairs += the sum of reach, *deepest = max(*deepest,
+// max ecc).  k_cl_ecc_rows: ecc in row order as int64.
+hipError_t k_cl_fold(const uint64_t* vis, LevelPlanes lvl, int nplanes, int64_t n, unsigned long long* far,
+                     unsigned long long* reach, int32_t* ecc, double* harm, hipStream_t s);
+hipError_t k_cl_finish(const unsigned long long* far, const unsigned long long* reach, const int32_t* ecc, int64_t n,
+                       double* close, unsigned long long* pairs, unsigned long long* deepest, hipStream_t s);
+hipError_t k_cl_ecc_rows(const int32_t* ecc, const int32_t* perm, int64_t* out, int64_t n, hipStream_t s);
 
 // PageRank gather diagnostics: [diag_lo, diag_hi) = only sources in this range are gathered
 // (the others read as 0; results invalid) — attributes the update's time to source ranges.

@@ -67,9 +67,10 @@ __device__ inline bool value_of(const ResArgs& a, const void* v0, const void* v1
         bits = static_cast<uint64_t>(d);
         return d != TGO_DIST_ABSENT;
     }
-    if (a.kind == TGO_RESULT_PAGERANK || a.kind == TGO_RESULT_TRIANGLES) {
-        // two 8-byte values on every executed vertex: the ranks and edge counts (doubles), or the
-        // triangle counts (int64) and clustering coefficients (doubles) — raw bits either way
+    if (a.kind == TGO_RESULT_PAGERANK || a.kind == TGO_RESULT_TRIANGLES || a.kind == TGO_RESULT_CLOSENESS) {
+        // two 8-byte values on every executed vertex: the ranks and edge counts (doubles), the
+        // triangle counts (int64) and clustering coefficients (doubles), or the closeness and
+        // harmonic centralities (doubles) — raw bits either way
         bits = static_cast<const uint64_t*>(k == 0 ? v0 : v1)[v];
         return true;
     }
@@ -184,16 +185,18 @@ int encode_results(const ResultSource& src, const tgo_result_args* a, const int3
                    std::string& err) {
     ResArgs ra{};
     ra.kind = a->kind;
-    ra.nkeys = a->kind == TGO_RESULT_PAGERANK || a->kind == TGO_RESULT_TRIANGLES ? 2 : 1;
+    ra.nkeys = a->kind == TGO_RESULT_PAGERANK || a->kind == TGO_RESULT_TRIANGLES || a->kind == TGO_RESULT_CLOSENESS ? 2 : 1;
     ra.rel_base = a->relation_id_base;
-    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_PEER_PRESSURE) { err = "unknown result kind"; return TGO_E_INVALID; }
-    int want[10][2] = {{TGO_DT_LONG, 0}, {TGO_DT_DOUBLE, TGO_DT_DOUBLE}, {TGO_DT_INTEGER, 0}, {0, 0}, {TGO_DT_LONG, 0},
-                       {TGO_DT_LONG, TGO_DT_DOUBLE}, {TGO_DT_LONG, 0}, {TGO_DT_LONG, 0}, {TGO_DT_DOUBLE, 0}, {TGO_DT_LONG, 0}};
+    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_CLOSENESS) { err = "unknown result kind"; return TGO_E_INVALID; }
+    int want[11][2] = {{TGO_DT_LONG, 0}, {TGO_DT_DOUBLE, TGO_DT_DOUBLE}, {TGO_DT_INTEGER, 0}, {0, 0}, {TGO_DT_LONG, 0},
+                       {TGO_DT_LONG, TGO_DT_DOUBLE}, {TGO_DT_LONG, 0}, {TGO_DT_LONG, 0}, {TGO_DT_DOUBLE, 0}, {TGO_DT_LONG, 0},
+                       {TGO_DT_DOUBLE, TGO_DT_DOUBLE}};
     // StandardSerializer registration numbers of the value classes (:71-81): Long 13, Double 20, Integer 12
     // (per key where a kind's two keys differ: the triangle count is a Long, its coefficient a Double)
-    uint8_t reg[10][2] = {{0x80 | 13, 0}, {0x80 | 20, 0x80 | 20}, {0x80 | 12, 0}, {0, 0}, {0x80 | 13, 0},
-                          {0x80 | 13, 0x80 | 20}, {0x80 | 13, 0}, {0x80 | 13, 0}, {0x80 | 20, 0}, {0x80 | 13, 0}};
-    static_assert(TGO_RESULT_PEER_PRESSURE == 9, "want / reg hold one row per result kind");
+    uint8_t reg[11][2] = {{0x80 | 13, 0}, {0x80 | 20, 0x80 | 20}, {0x80 | 12, 0}, {0, 0}, {0x80 | 13, 0},
+                          {0x80 | 13, 0x80 | 20}, {0x80 | 13, 0}, {0x80 | 13, 0}, {0x80 | 20, 0}, {0x80 | 13, 0},
+                          {0x80 | 20, 0x80 | 20}};
+    static_assert(TGO_RESULT_CLOSENESS == 10, "want / reg hold one row per result kind");
     const bool long_or_int = a->kind == TGO_RESULT_COMPONENT || a->kind == TGO_RESULT_TRIANGLES || a->kind == TGO_RESULT_CORE ||
                              a->kind == TGO_RESULT_SCC || a->kind == TGO_RESULT_PEER_PRESSURE;
     if (long_or_int) {
@@ -230,7 +233,7 @@ int encode_results(const ResultSource& src, const tgo_result_args* a, const int3
         if (a->datatypes[k] == TGO_DT_OBJECT) {
             lead[k] = reg[a->kind][k];                     // generic key: writeClassAndObject
         } else if (a->datatypes[k] != want[a->kind][k]) {
-            err = "compute key datatype must be Long (distance), Double (pageRank, edgeCount, clustering coefficient), "
+            err = "compute key datatype must be Long (distance), Double (pageRank, edgeCount, clustering coefficient, closeness, harmonic), "
                   "Integer (degree), Long or Integer (component, cluster, triangles, core number), Double (betweenness) or generic (Object)";
             return TGO_E_UNSUPPORTED;
         }

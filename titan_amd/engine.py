@@ -463,6 +463,50 @@ class Engine:
         _check(self.lib, self.ctx, self.lib.tgo_copy_peer_pressure(self.ctx, L.ptr(out, C.c_int64)))
         return out
 
+    def closeness(self, seeds=None, dense=False, max_depth=None, fetch=True, scope=L.SCOPE_BOTH_E):
+        """Closeness and harmonic centrality over the loaded scope (tgo_closeness), folded on the device
+        out of 64-source sweeps.  seeds: Titan ids (dense: row-order indices) whose distances are
+        accumulated in the order given, in batches of 64; None = every vertex (exact values).  A vertex
+        accumulates its distances from the seeds: in-closeness along the direction of message flow,
+        symmetric on bothE; the values are unnormalised.  max_depth: a distance above it counts as not
+        reached (None: no cut).  scope: the scope this engine was loaded for (the distances are
+        tgo_bfs_multi's on it).  (dict(closeness, harmonic), info): float64 arrays in row order
+        (None when fetch is False: the result stays on the device for copy_closeness / result_rows);
+        closeness = reach / far (0.0 without a reaching seed), harmonic = the sum of 1 / d in the
+        contractual fold order; info = dict(sources, reached_pairs, batches, max_depth)."""
+        if max_depth is None:
+            max_depth = 2**31 - 1
+        if not 0 <= int(max_depth) <= 2**31 - 1:
+            raise ValueError("max_depth must be in [0, 2^31 - 1]")
+        a = L.ClArgs(int(scope), 0, int(max_depth), 1 if dense else 0)
+        info = L.ClInfo()
+        if seeds is None:
+            sd, nseeds = None, -1
+        else:
+            sd = np.ascontiguousarray(seeds, dtype=np.int64)
+            if sd.ndim != 1:
+                raise ValueError("seeds must be one-dimensional")
+            nseeds = len(sd)
+            if nseeds == 0:
+                sd = None
+        cl = np.zeros(self.n, dtype=np.float64) if fetch else None
+        ha = np.zeros(self.n, dtype=np.float64) if fetch else None
+        _check(self.lib, self.ctx, self.lib.tgo_closeness(self.ctx, C.byref(a), L.ptr(sd, C.c_int64), nseeds,
+                                                          L.ptr(cl, C.c_double), L.ptr(ha, C.c_double), C.byref(info)))
+        return ({"closeness": cl, "harmonic": ha},
+                {"sources": int(info.sources), "reached_pairs": int(info.reached_pairs),
+                 "batches": int(info.batches), "max_depth": int(info.max_depth)})
+
+    def copy_closeness(self):
+        """The five arrays of the last closeness() run, in row order: dict(far, reach, ecc (int64),
+        closeness, harmonic (float64))."""
+        far, reach, ecc = (np.zeros(self.n, dtype=np.int64) for _ in range(3))
+        cl, ha = (np.zeros(self.n, dtype=np.float64) for _ in range(2))
+        _check(self.lib, self.ctx, self.lib.tgo_copy_closeness(
+            self.ctx, L.ptr(far, C.c_int64), L.ptr(reach, C.c_int64), L.ptr(ecc, C.c_int64),
+            L.ptr(cl, C.c_double), L.ptr(ha, C.c_double)))
+        return {"far": far, "reach": reach, "ecc": ecc, "closeness": cl, "harmonic": ha}
+
     def result_rows(self, kind, key_ids, datatypes, relation_id_base):
         """Edgestore entries of the last program's compute keys (tgo_result_rows): the rows
         ResultMode PERSIST writes back (FulgoraGraphComputer.java:248-305)."""
