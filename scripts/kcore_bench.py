@@ -7,7 +7,7 @@ first call minus its kernel time), and the result's figures.
                                   [--sweep] [--host 1] [--threads 16] [--generic 1]
 
 --sweep    times TGO_TUNE_CORE_TAIL, then TGO_TUNE_CORE_WAVE_ROW and TGO_TUNE_CORE_LDS_QUEUE at the
-           best tail (DESIGN.md 4.6 records the sweep the defaults in api_analytics.cpp come from).
+           best tail (DESIGN.md 4.6 records the sweep the defaults in api_kcore.cpp come from).
 --host     rebuilds the projection on the host from the assembled device lists and peels it with
            --threads threads (scripts/kcore_host.cpp, compiled on first use); checks the device's
            core numbers against it.

@@ -7,7 +7,7 @@ of the first call minus its kernel time), and the counts.
                                       [--sweep] [--host 1] [--threads 16]
 
 --sweep  times TGO_TUNE_TRI_BLOCK_ROW without wave rows (wave row = block row), then
-         TGO_TUNE_TRI_WAVE_ROW below the best block row (the defaults in api_analytics.cpp were chosen from this).
+         TGO_TUNE_TRI_WAVE_ROW below the best block row (the defaults in api_tri.cpp were chosen from this).
 --host   rebuilds the forward lists on the host from the assembled device lists
          (scripts/tri_host_count.cpp, compiled on first use): the work measure
          sum min(|fwd(c)|, |fwd(b)|) over oriented entries and a --threads host count of the same

@@ -1,6 +1,7 @@
 // api.cpp — the C-ABI (include/titan_gpu_olap.h): the context's lifecycle and tuning, graph accessors,
-// stats.  Loads: api_load.cpp; program drivers: api_traverse, api_msbfs, api_analytics, api_pagerank,
-// api_generic (with the result write-back), api_part; ctx.hpp and program.hpp hold what they share.
+// stats.  Loads: api_load.cpp; program drivers: api_traverse, api_msbfs, api_pagerank, api_generic (with
+// the result write-back), api_part, and one file per analytic (api_cc, api_tri, api_kcore, api_scc,
+// api_bc, api_pp, api_cl); ctx.hpp and program.hpp hold what they share, tuning.hpp the knobs' table.
 //
 // The program drivers replace FulgoraGraphComputer.submit's superstep loop
 // (FulgoraGraphComputer.java:151-189): instead of one full edgestore scan per superstep,
@@ -75,24 +76,6 @@ int check_program(tgo_ctx* ctx, int scope) {
     return TGO_OK;
 }
 
-// wait_publish for a publish that later ones may have overwritten: spin until the sequence
-// word reaches seq (the words then hold that publish or a later one).
-int wait_publish_at_least(tgo_ctx* ctx, unsigned long long seq) {
-    Scratch& s = ctx->sc;
-    const volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(s.hcnt) + kCounterWords;
-    for (uint64_t it = 1;; ++it) {
-        if (*flag >= seq) break;
-        if ((it & 0x3FFF) == 0) {
-            const hipError_t q = hipStreamQuery(ctx->stream);
-            if (q != hipSuccess && q != hipErrorNotReady) return fail(ctx, TGO_E_HIP, hipGetErrorString(q));
-            if (q == hipSuccess && *flag < seq) return fail(ctx, TGO_E_HIP, "loop state publish not visible after the stream drained");
-        }
-        __builtin_ia32_pause();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return TGO_OK;
-}
-
 }  // namespace tgo
 
 extern "C" {
@@ -107,117 +90,13 @@ void tgo_default_options(tgo_options* o) {
     o->stream = nullptr;
 }
 
+// the bounds tuning.hpp repeats, since it includes no engine header
+static_assert(kTuneCoreQueue == kCoreQueue && kTuneMsHeadMax == kMsHeadMax && kTunePpMinSlots == kPpMinSlots &&
+                  kTunePpMaxSlots == kPpMaxSlots, "tuning.hpp: bounds out of step with engine.hpp");
+
 int tgo_set_tuning(tgo_ctx* ctx, int32_t key, double value) {
     if (!ctx) return TGO_E_INVALID;
-    switch (key) {
-    case TGO_TUNE_MS_SPLIT:
-        if (!(value <= 1.0)) return fail(ctx, TGO_E_INVALID, "TGO_TUNE_MS_SPLIT: a fraction <= 1 (< 0: the default)");
-        ctx->ms_split = value < 0.0 ? -1.0 : value;
-        return TGO_OK;
-    case TGO_TUNE_MS_GHOST:
-        if (value != 0.0 && value != 1.0) return fail(ctx, TGO_E_INVALID, "TGO_TUNE_MS_GHOST: 0 or 1");
-        ctx->ms_ghost = value != 0.0 ? 1 : 0;
-        return TGO_OK;
-    case TGO_TUNE_DS_BINS:
-        if (value != 0.0 && value != 1.0 && value != -1.0) return fail(ctx, TGO_E_INVALID, "TGO_TUNE_DS_BINS: 0, 1 or -1");
-        ctx->ds_bins = static_cast<int>(value);
-        return TGO_OK;
-    case TGO_TUNE_DS_DONE:
-        if (value != 0.0 && value != 1.0 && value != -1.0) return fail(ctx, TGO_E_INVALID, "TGO_TUNE_DS_DONE: 0, 1 or -1");
-        ctx->ds_done = static_cast<int>(value);
-        return TGO_OK;
-    case TGO_TUNE_DS_SMALL:
-        if (value != 0.0 && value != 1.0 && value != -1.0) return fail(ctx, TGO_E_INVALID, "TGO_TUNE_DS_SMALL: 0, 1 or -1");
-        ctx->ds_small = static_cast<int>(value);
-        return TGO_OK;
-    case TGO_TUNE_DS_PULL:
-        if (!(value >= -1.0) || value > 1.0) return fail(ctx, TGO_E_INVALID, "TGO_TUNE_DS_PULL: a fraction in [0, 1] or -1");
-        ctx->ds_pull = value;
-        return TGO_OK;
-    case TGO_TUNE_MS_COLD:
-        if (!(value >= -1.0) || value >= 2147483647.0 || value != static_cast<double>(static_cast<int64_t>(value)))
-            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_MS_COLD: -1, 0, 1 or a hot-head size > 1");
-        ctx->ms_cold = static_cast<int64_t>(value);
-        return TGO_OK;
-    case TGO_TUNE_MS_STAY:
-        if (!((value >= 0.0 && value <= 1.0e18) || value == -1.0))
-            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_MS_STAY: gamma >= 0 (0 = off) or -1 (the default)");
-        ctx->ms_stay = value;
-        return TGO_OK;
-    case TGO_TUNE_MS_SPARSE:
-        if (!((value >= 0.0 && value <= 1.0e18) || value == -1.0))
-            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_MS_SPARSE: a fraction >= 0 (0 = off) or -1 (the default)");
-        ctx->ms_sparse = value;
-        return TGO_OK;
-    case TGO_TUNE_MS_HEAD:
-        if (!((value >= 0.0 && value <= static_cast<double>(kMsHeadMax)) || value == -1.0) ||
-            value != static_cast<double>(static_cast<int64_t>(value)))
-            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_MS_HEAD: a whole number of entries in [0, 2^20] (0 = off) or -1 (the default)");
-        ctx->ms_head = static_cast<int64_t>(value);
-        return TGO_OK;
-    case TGO_TUNE_DS_PILE_CAP:
-        if (!(value >= 0.0) || value > 9.0e15) return fail(ctx, TGO_E_INVALID, "TGO_TUNE_DS_PILE_CAP: entries >= 0");
-        ctx->ds_pile_cap = static_cast<int64_t>(value);
-        return TGO_OK;
-    case TGO_TUNE_TRI_WAVE_ROW:
-    case TGO_TUNE_TRI_BLOCK_ROW: {
-        if (!(value < 0.0) && !(value >= 1.0 && value <= 9.0e15 && value == static_cast<double>(static_cast<int64_t>(value))))
-            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_TRI_WAVE_ROW / _BLOCK_ROW: a row length >= 1 (< 0: the default)");
-        (key == TGO_TUNE_TRI_WAVE_ROW ? ctx->tri_wave_row : ctx->tri_block_row) = value < 0.0 ? -1 : static_cast<int64_t>(value);
-        return TGO_OK;
-    }
-    case TGO_TUNE_CORE_WAVE_ROW:
-        if (!(value < 0.0) && !(value >= 1.0 && value <= 9.0e15 && value == static_cast<double>(static_cast<int64_t>(value))))
-            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_CORE_WAVE_ROW: a neighbourhood size >= 1 (< 0: the default)");
-        ctx->core_wave_row = value < 0.0 ? -1 : static_cast<int64_t>(value);
-        return TGO_OK;
-    case TGO_TUNE_CORE_TAIL:
-        if (!(value < 0.0) && !(value <= 9.0e15 && value == static_cast<double>(static_cast<int64_t>(value))))
-            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_CORE_TAIL: a whole number of vertices >= 0 (0 = never; < 0: the default)");
-        ctx->core_tail = value < 0.0 ? -1 : static_cast<int64_t>(value);
-        return TGO_OK;
-    case TGO_TUNE_CORE_LDS_QUEUE:
-        if (!(value < 0.0) && !(value >= 1.0 && value <= static_cast<double>(kCoreQueue) &&
-                                value == static_cast<double>(static_cast<int64_t>(value))))
-            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_CORE_LDS_QUEUE: entries in [1, 4096] (< 0: the default)");
-        ctx->core_lds_queue = value < 0.0 ? -1 : static_cast<int64_t>(value);
-        return TGO_OK;
-    case TGO_TUNE_SCC_WAVE_ROW:
-        if (!(value < 0.0) && !(value >= 1.0 && value <= 9.0e15 && value == static_cast<double>(static_cast<int64_t>(value))))
-            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_SCC_WAVE_ROW: a row length >= 1 (< 0: the default)");
-        ctx->scc_wave_row = value < 0.0 ? -1 : static_cast<int64_t>(value);
-        return TGO_OK;
-    case TGO_TUNE_SCC_TAIL:
-        if (!(value < 0.0) && !(value <= 9.0e15 && value == static_cast<double>(static_cast<int64_t>(value))))
-            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_SCC_TAIL: a whole number of vertices >= 0 (0 = never; < 0: the default)");
-        ctx->scc_tail = value < 0.0 ? -1 : static_cast<int64_t>(value);
-        return TGO_OK;
-    case TGO_TUNE_SCC_TRIM:
-    case TGO_TUNE_SCC_PIVOT:
-        if (!(value < 0.0) && value != 0.0 && value != 1.0)
-            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_SCC_TRIM / _PIVOT: 0 (the phase is skipped) or 1 (< 0: the default)");
-        (key == TGO_TUNE_SCC_TRIM ? ctx->scc_trim : ctx->scc_pivot) = value < 0.0 ? -1 : static_cast<int>(value);
-        return TGO_OK;
-    case TGO_TUNE_BC_WAVE_ROW:
-        if (!(value < 0.0) && !(value >= 1.0 && value <= 9.0e15 && value == static_cast<double>(static_cast<int64_t>(value))))
-            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_BC_WAVE_ROW: a row length >= 1 (< 0: the default)");
-        ctx->bc_wave_row = value < 0.0 ? -1 : static_cast<int64_t>(value);
-        return TGO_OK;
-    case TGO_TUNE_PP_WAVE_ROW:
-    case TGO_TUNE_PP_BLOCK_ROW:
-        if (!(value < 0.0) && !(value >= 1.0 && value <= 9.0e15 && value == static_cast<double>(static_cast<int64_t>(value))))
-            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_PP_WAVE_ROW / _BLOCK_ROW: a row length >= 1 (< 0: the default)");
-        (key == TGO_TUNE_PP_WAVE_ROW ? ctx->pp_wave_row : ctx->pp_block_row) = value < 0.0 ? -1 : static_cast<int64_t>(value);
-        return TGO_OK;
-    case TGO_TUNE_PP_SLOTS:
-        if (!(value < 0.0) && !(value >= static_cast<double>(kPpMinSlots) && value <= static_cast<double>(kPpMaxSlots) &&
-                                value == static_cast<double>(static_cast<int64_t>(value))))
-            return fail(ctx, TGO_E_INVALID, "TGO_TUNE_PP_SLOTS: table entries per wave in [16, 1024] (< 0: the default)");
-        ctx->pp_slots = value < 0.0 ? -1 : static_cast<int64_t>(value);
-        return TGO_OK;
-    default:
-        return fail(ctx, TGO_E_INVALID, "tgo_set_tuning: unknown key");
-    }
+    return tuning_set(ctx->tune, key, value, ctx->err);
 }
 
 int tgo_create(const tgo_options* opts, tgo_ctx** out) {

@@ -30,22 +30,22 @@ int ms_alloc(tgo_ctx* ctx) {
 // the list entries (default 0.5 %)
 double ms_split_of(const tgo_ctx* ctx) {
     static const double env = env_double("TGO_MS_SPLIT", 0.005);
-    return tuned(ctx->ms_split, env);
+    return tuned(ctx->tune.f64(TGO_TUNE_MS_SPLIT), env);
 }
 // gamma of the stay-in-pull rule, and the sparse push levels' fraction of n_active (tgo_bfs_multi)
 double ms_stay_of(const tgo_ctx* ctx) {
     static const double env = env_clamped("TGO_MS_STAY", kMsStayDefault, 0.0, HUGE_VAL);
-    return tuned(ctx->ms_stay, env);
+    return tuned(ctx->tune.f64(TGO_TUNE_MS_STAY), env);
 }
 double ms_sparse_of(const tgo_ctx* ctx) {
     static const double env = env_clamped("TGO_MS_SPARSE", kMsSparseDefault, 0.0, HUGE_VAL);
-    return tuned(ctx->ms_sparse, env);
+    return tuned(ctx->tune.f64(TGO_TUNE_MS_SPARSE), env);
 }
 // head probe of ms_pull's long lists, in entries (clamped before the cast)
 int64_t ms_head_of(const tgo_ctx* ctx) {
     static const int64_t env = static_cast<int64_t>(
         env_clamped("TGO_MS_HEAD", static_cast<double>(kMsHeadDefault), 0.0, static_cast<double>(kMsHeadMax)));
-    return tuned(ctx->ms_head, env);
+    return tuned(ctx->tune.i64(TGO_TUNE_MS_HEAD), env);
 }
 
 }  // namespace tgo
@@ -163,7 +163,7 @@ int run_ms_sweep(tgo_ctx* ctx, const int64_t* in, int32_t nseeds, int32_t max_de
     int64_t mu = -1;            // after a pull level: list entries of the still-open vertices (< 0: not counted)
     bool level0_sparse = false, last_sparse = false;
     unsigned long long se_pub[TGO_MAX_SOURCES] = {};   // the per-source entries the last settle published
-    const volatile unsigned long long* hw = reinterpret_cast<volatile unsigned long long*>(s.hcnt);
+    const volatile unsigned long long* hw = host_words(ctx);
     for (int L = 0; L < depth && qlen > 0; ++L) {
         const bool stay = pulled && mu >= 0 && stay_gamma > 0.0 &&
                           static_cast<double>(mu) <= stay_gamma * static_cast<double>(mf);
@@ -235,9 +235,7 @@ int run_ms_sweep(tgo_ctx* ctx, const int64_t* in, int32_t nseeds, int32_t max_de
                     if (!nx_clean) HIP_TRY(hipMemsetAsync(nx, 0, g.n_active * 8, st));
                     if (any) {                           // push the sparse sources' frontiers
                         HIP_TRY(k_ms_queue(push, g.n_active, fr, s.q[cur ^ 1], s.qdeg, s.cnt, st, sparse));
-                        const unsigned long long sseq = ++s.pub_seq;         // the counters zero again after it
-                        HIP_TRY(k_publish_turn(s.cnt, s.hcnt_dev, sseq, nullptr, st));
-                        if ((rc = wait_publish(ctx, sseq))) return rc;
+                        if ((rc = turn(ctx))) return rc;         // the counters zero again after it
                         const int64_t sq = static_cast<int64_t>(s.hcnt->qlen);
                         if (sq > 0) {
                             if ((rc = scan_frontier(ctx, sq))) return rc;
@@ -259,9 +257,10 @@ int run_ms_sweep(tgo_ctx* ctx, const int64_t* in, int32_t nseeds, int32_t max_de
             // cold entry of every row to reach them.
             MsColdSplit cs;
             static const bool cold_env = env_double("TGO_MS_COLD", 0.0) != 0.0;
-            const bool cold_on = tuned_on(ctx->ms_cold, cold_env);
+            const int64_t cold = ctx->tune.i64(TGO_TUNE_MS_COLD);
+            const bool cold_on = tuned_on(cold, cold_env);
             if (cold_on && !prev_pull && !filter) {
-                if ((rc = ms_cold_layout(ctx, scope, pull, ctx->ms_cold))) return rc;
+                if ((rc = ms_cold_layout(ctx, scope, pull, cold))) return rc;
                 if (g.msc_C > 0) {
                     cs.hot_lim = g.msc_hot;
                     cs.acc = s.ms_cacc;
@@ -349,8 +348,8 @@ int run_ms_sweep(tgo_ctx* ctx, const int64_t* in, int32_t nseeds, int32_t max_de
             // level planes, zeroed counters) before the host waits: the GPU runs it during the
             // host's round trip (≈ 10–25 us a level)
             // (the same launch zeroes the counters, and publishes and zeroes the per-source sums)
-            const unsigned long long seq = ++s.pub_seq;
-            HIP_TRY(k_publish_turn(s.cnt, s.hcnt_dev, seq, sums ? s.ms_srcent : nullptr, st));
+            unsigned long long seq = 0;
+            if ((rc = turn_begin(ctx, seq, sums ? s.ms_srcent : nullptr))) return rc;
             cnt_zero = true;
             if (sums) s.ms_srcent_zero = true;
             if (L + 1 < depth && (rc = ms_planes_for(ctx, L + 2))) return rc;

@@ -1056,8 +1056,7 @@ int part_sssp_header_read(tgo_ctx* ctx, const int64_t* own, const int64_t* recv,
     const unsigned long long seq = ++s.pub_seq;
     HIP_TRY(k_ds_header_fold(own, recv, nranks, out, ctx->stream, s.hcnt_dev, seq));
     if (int rc = wait_publish(ctx, seq)) return rc;
-    const volatile unsigned long long* w = reinterpret_cast<volatile unsigned long long*>(s.hcnt);
-    for (int i = 0; i < count; ++i) words[i] = static_cast<int64_t>(w[i]);
+    for (int i = 0; i < count; ++i) words[i] = static_cast<int64_t>(host_words(ctx)[i]);
     return TGO_OK;
 }
 // Switch the run tgo_part_sssp_begin started onto the light/heavy split at bucket width delta
@@ -1138,8 +1137,7 @@ int part_sssp_dev_relax(tgo_ctx* ctx, int32_t nranks, int64_t* send, int64_t* si
         const unsigned long long seq = ++s.pub_seq;
         HIP_TRY(k_ds_part_header(counts, nranks, s.ds_loop, ctx->part_cur, offs, cursor, sizes, st, s.hcnt_dev, seq));
         if (int rc = wait_publish(ctx, seq)) return rc;
-        const volatile unsigned long long* w = reinterpret_cast<volatile unsigned long long*>(s.hcnt);
-        for (int i = 0; i < 5; ++i) fold[i] = static_cast<int64_t>(w[i]);
+        for (int i = 0; i < 5; ++i) fold[i] = static_cast<int64_t>(host_words(ctx)[i]);
         return TGO_OK;
     }
     HIP_TRY(k_ds_part_header(counts, nranks, s.ds_loop, ctx->part_cur, offs, cursor, sizes, st));
@@ -1163,17 +1161,10 @@ int part_sssp_dev_extract(tgo_ctx* ctx, int64_t thr) {
                               ctx->part_cur, thr, ctx->stream));
     return TGO_OK;
 }
-// `count` device words (on the ctx stream, after the work queued so far) to out, through the
-// host-mapped counter page: one tiny kernel and a spin instead of a copy and a stream wait.
+// read_words (ctx.hpp) for part_driver.cpp's loops: at most one publish of words.
 int part_read_words(tgo_ctx* ctx, const int64_t* dev, int count, int64_t* out) {
-    Scratch& s = ctx->sc;
-    if (!s.hcnt || count < 0 || count > kCounterWords) return fail(ctx, TGO_E_STATE, "part_read_words");
-    const unsigned long long seq = ++s.pub_seq;
-    HIP_TRY(k_publish_words(dev, count, s.hcnt_dev, seq, ctx->stream));
-    if (int rc = wait_publish(ctx, seq)) return rc;
-    const volatile unsigned long long* w = reinterpret_cast<volatile unsigned long long*>(s.hcnt);
-    for (int i = 0; i < count; ++i) out[i] = static_cast<int64_t>(w[i]);
-    return TGO_OK;
+    if (!ctx->sc.hcnt || count < 0 || count > kCounterWords) return fail(ctx, TGO_E_STATE, "part_read_words");
+    return read_words(ctx, dev, count, out);
 }
 // The next multi-source settle also sums the new frontier's push entries per source into
 // out (64 words, zeroed here on the ctx stream): the native driver's split after that level

@@ -45,10 +45,8 @@ int run_bfs(tgo_ctx* ctx, int64_t seed, int max_depth, int scope) {
         for (int L = 0; L < max_depth && qlen > 0; ++L) {
             if (mf < 0) {   // degree of the seed, through the mapped counter page (a copy and a
                             // stream synchronisation cost ~30 us before the first level)
-                const unsigned long long seq = ++s.pub_seq;
-                HIP_TRY(k_publish_words(s.qdeg, 1, s.hcnt_dev, seq, st));
-                if (int rc = wait_publish(ctx, seq)) return rc;
-                const int64_t d = static_cast<int64_t>(reinterpret_cast<volatile unsigned long long*>(s.hcnt)[0]);
+                int64_t d = 0;
+                if (int rc = read_words(ctx, s.qdeg, 1, &d)) return rc;
                 mf = d;
                 mu -= d;
             }
@@ -167,14 +165,14 @@ int run_delta_device(tgo_ctx* ctx, int64_t seed, int64_t delta, bool force_scan)
     // most bucket k + 1 + (max_weight - 1) / delta, so that many + 1 piles in a ring hold every
     // pending vertex; wider weight ranges keep the bitmap-scan loop.
     static const bool bins_env = env_double("TGO_DS_BINS", 1.0) != 0.0;
-    const bool bins_on = tuned_on(ctx->ds_bins, bins_env);
+    const bool bins_on = tuned_on(ctx->tune.i64(TGO_TUNE_DS_BINS), bins_env);
     const int64_t reach = 2 + (std::max<int64_t>(g.max_weight, 1) - 1) / delta;
     const int nbins = (bins_on && !force_scan && reach <= kDsMaxBins) ? static_cast<int>(reach) : 0;
     // TGO_DS_DONE=1: the relax skips the distance read of done targets (measured neutral at
     // RMAT-24: the largest phases come before most vertices are done); TGO_DS_PILE_SCAN: piles
     // above this fraction of n are extracted by the bitmap scan
     static const bool done_env = env_double("TGO_DS_DONE", 0.0) != 0.0;
-    const bool done_filter = tuned_on(ctx->ds_done, done_env);
+    const bool done_filter = tuned_on(ctx->tune.i64(TGO_TUNE_DS_DONE), done_env);
     static const double pile_scan = env_double("TGO_DS_PILE_SCAN", 1.0 / 16.0);
     const int64_t scan_above = static_cast<int64_t>(pile_scan * static_cast<double>(n));
     if (!s.ds_loop) {
@@ -185,7 +183,8 @@ int run_delta_device(tgo_ctx* ctx, int64_t seed, int64_t delta, bool force_scan)
         HIP_TRY(dev_alloc(ctx, s.ds_loop, 1));
         ctx->st.device_bytes = ctx->dev_bytes;
     }
-    const int64_t cap = ctx->ds_pile_cap > 0 ? ctx->ds_pile_cap : std::max<int64_t>(n, 1024);
+    const int64_t cap_set = ctx->tune.i64(TGO_TUNE_DS_PILE_CAP);
+    const int64_t cap = cap_set > 0 ? cap_set : std::max<int64_t>(n, 1024);
     if (nbins && s.ds_pile && s.ds_pile_cap != cap) {
         dev_free(ctx, s.ds_pile, kDsMaxBins * s.ds_pile_cap);
         s.ds_pile_cap = 0;
@@ -203,7 +202,7 @@ int run_delta_device(tgo_ctx* ctx, int64_t seed, int64_t delta, bool force_scan)
     // least that many members has its heavy entries pulled by the vertices that can still
     // improve (delta_loop.hip ds_pull_heavy) instead of pushed entry by entry.
     static const double pull_env = env_double("TGO_DS_PULL", 0.0);
-    const double pull_frac = tuned(ctx->ds_pull, pull_env);
+    const double pull_frac = tuned(ctx->tune.f64(TGO_TUNE_DS_PULL), pull_env);
     DsPull pull{};
     if (nbins && pull_frac > 0) {
         const int64_t words = (n + 63) / 64 + 1;
@@ -228,7 +227,7 @@ int run_delta_device(tgo_ctx* ctx, int64_t seed, int64_t delta, bool force_scan)
     // (profiles/r05ss1_sssp_small_ab.log) — a tiny step is a chain of dependent memory
     // round trips either way, and one block pays them with fewer loads in flight.
     static const bool small_env = env_double("TGO_DS_SMALL", 0.0) != 0.0;
-    const bool small_on = tuned_on(ctx->ds_small, small_env);
+    const bool small_on = tuned_on(ctx->tune.i64(TGO_TUNE_DS_SMALL), small_env);
     const bool small = small_on && nbins && !done_filter && pull.min_members == 0;
     // every step either relaxes a non-empty queue or extracts (at most one extraction in a row
     // takes nothing); a run needs far fewer than 4n + 64 steps — the bound only stops a bug
@@ -262,8 +261,8 @@ int run_delta_device(tgo_ctx* ctx, int64_t seed, int64_t delta, bool force_scan)
             const unsigned long long seq = ++s.pub_seq;
             HIP_TRY(k_ds_publish(s.ds_loop, s.hcnt_dev, seq, st));
             if (pending) {
-                if (int rc = wait_publish_at_least(ctx, pending)) return rc;
-                const volatile unsigned long long* hw = reinterpret_cast<volatile unsigned long long*>(s.hcnt);
+                if (int rc = wait_publish(ctx, pending, true)) return rc;
+                const volatile unsigned long long* hw = host_words(ctx);
                 if (hw[1]) return fail(ctx, TGO_E_PROGRAM, "vertex program failed: a traversed edge has no value for the weight property");
                 stop = hw[0] != 0 || hw[2] != 0;
             }
@@ -498,10 +497,7 @@ int finish_distance_program(tgo_ctx* ctx, int scope, int flags, int64_t* dist_ou
 extern "C" {
 
 int tgo_bfs(tgo_ctx* ctx, const tgo_bfs_args* a, int64_t* dist_out) {
-    if (!ctx) return TGO_E_INVALID;
-    ctx->res_kind = -1;
-    if (!a) return fail(ctx, TGO_E_INVALID, "null args");
-    int rc = check_program(ctx, a->scope);
+    int rc = program_open(ctx, a);
     if (rc) return rc;
     if (a->max_depth < 0) return fail(ctx, TGO_E_INVALID, "max_depth < 0");
     (void)hipSetDevice(ctx->opts.device);
@@ -513,10 +509,7 @@ int tgo_bfs(tgo_ctx* ctx, const tgo_bfs_args* a, int64_t* dist_out) {
 }
 
 int tgo_sssp(tgo_ctx* ctx, const tgo_sssp_args* a, int64_t* dist_out) {
-    if (!ctx) return TGO_E_INVALID;
-    ctx->res_kind = -1;
-    if (!a) return fail(ctx, TGO_E_INVALID, "null args");
-    int rc = check_program(ctx, a->scope);
+    int rc = program_open(ctx, a);
     if (rc) return rc;
     if (a->max_depth < 0) return fail(ctx, TGO_E_INVALID, "max_depth < 0");
     if (a->mode != TGO_SSSP_HOP_BOUNDED && a->mode != TGO_SSSP_DELTA) return fail(ctx, TGO_E_INVALID, "invalid mode");

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime_api.h>
 #include "engine.hpp"
 #include "trace.hpp"
+#include "tuning.hpp"
 #include "../../include/titan_gpu_olap_part.h"
 
 struct tgo_ctx {
@@ -69,38 +70,12 @@ struct tgo_ctx {
     bool res_empty = false;                  // it set no property (PageRank iterations(0))
     tgo::ResultSource res_src;
     int num_cus = 256;          // compute units of the device (persistent launches)
-    double ms_split = -1.0;     // tgo_set_tuning(TGO_TUNE_MS_SPLIT); < 0: TGO_MS_SPLIT / the default
-    int ms_ghost = 1;           // tgo_set_tuning(TGO_TUNE_MS_GHOST): dense partitioned levels exchange ghosts
-    int ds_bins = -1;           // tgo_set_tuning(TGO_TUNE_DS_BINS): 1 / 0; < 0: TGO_DS_BINS / on
-    int64_t ds_pile_cap = 0;    // tgo_set_tuning(TGO_TUNE_DS_PILE_CAP): entries per pile; 0 = n
-    int ds_done = -1;           // tgo_set_tuning(TGO_TUNE_DS_DONE): 1 / 0; < 0: TGO_DS_DONE / off
-    double ds_pull = -1;        // tgo_set_tuning(TGO_TUNE_DS_PULL): member fraction; < 0: TGO_DS_PULL / off
-    int ds_small = -1;          // tgo_set_tuning(TGO_TUNE_DS_SMALL): 1 / 0; < 0: TGO_DS_SMALL / off
+    tgo::Tuning tune;           // tgo_set_tuning (tuning.hpp): one value per TGO_TUNE_* key
     unsigned long long* part_srcent = nullptr;   // next settle's per-source sums (part_ms_settle_sums)
     bool part_count_only = false;               // next settle: no queue (part_ms_settle_sums)
     uint64_t* part_own_next = nullptr;          // next push: owned targets straight into these masks
     uint64_t* part_own_direct = nullptr;        // the last push did so (its settle skips the own OR)
-    int64_t ms_cold = -1;       // tgo_set_tuning(TGO_TUNE_MS_COLD): 0 off, 1 on, > 1 on with that
-                                // hot head (and segment); < 0: TGO_MS_COLD / on
-    double ms_stay = -1.0;      // tgo_set_tuning(TGO_TUNE_MS_STAY): gamma; < 0: TGO_MS_STAY / the default
-    double ms_sparse = -1.0;    // tgo_set_tuning(TGO_TUNE_MS_SPARSE): fraction of n_active; < 0: TGO_MS_SPARSE / the default
-    int64_t ms_head = -1;       // tgo_set_tuning(TGO_TUNE_MS_HEAD): entries, 0 = off; < 0: TGO_MS_HEAD / the default
-    int64_t tri_wave_row = -1;  // tgo_set_tuning(TGO_TUNE_TRI_WAVE_ROW / _BLOCK_ROW): forward-row lengths from
-    int64_t tri_block_row = -1; // which a wave / a workgroup takes the row; < 0: the defaults (kTriWaveRow / kTriBlockRow)
     int64_t tri_max = 0;        // largest count of the last tgo_triangles (an Integer key's range check)
-    int64_t core_wave_row = -1; // tgo_set_tuning(TGO_TUNE_CORE_WAVE_ROW): neighbourhood size from which a wave walks it
-    int64_t core_tail = -1;     // tgo_set_tuning(TGO_TUNE_CORE_TAIL): alive vertices one workgroup finishes; 0 = never
-    int64_t core_lds_queue = -1;    // tgo_set_tuning(TGO_TUNE_CORE_LDS_QUEUE): entries of a workgroup's own queue
-                                // (< 0: the defaults kCoreWaveRow / kCoreTail / kCoreLdsQueue)
-    int64_t scc_wave_row = -1;  // tgo_set_tuning(TGO_TUNE_SCC_WAVE_ROW): row length from which a wave walks it
-    int64_t scc_tail = -1;      // tgo_set_tuning(TGO_TUNE_SCC_TAIL): live vertices one workgroup finishes; 0 = never
-    int scc_trim = -1;          // tgo_set_tuning(TGO_TUNE_SCC_TRIM / _PIVOT): 0 = the phase is skipped
-    int scc_pivot = -1;         // (< 0: the defaults kSccWaveRow / kSccTailDefault, both phases on)
-    int64_t bc_wave_row = -1;   // tgo_set_tuning(TGO_TUNE_BC_WAVE_ROW): row length from which a wave sums it
-                                // (< 0: the default kBcWaveRow)
-    int64_t pp_wave_row = -1;   // tgo_set_tuning(TGO_TUNE_PP_WAVE_ROW / _BLOCK_ROW): receive-row lengths from which
-    int64_t pp_block_row = -1;  // a wave / a workgroup tallies the row; TGO_TUNE_PP_SLOTS: table entries per wave
-    int64_t pp_slots = -1;      // (< 0: the defaults kPpWaveRow / kPpBlockRow / kPpSlots)
     // state a native partitioned driver keeps between runs on this graph (part_driver.cpp:
     // the PageRank ghost lists); dropped with the graph
     std::shared_ptr<void> part_state;
@@ -172,27 +147,33 @@ void free_graph(tgo_ctx* ctx);
 int threads_of(const tgo_ctx* ctx);
 int resolve_seed(tgo_ctx* ctx, int64_t seed, int is_dense, int64_t& out);
 int check_program(tgo_ctx* ctx, int scope);
-// wait_publish for a publish that later ones may have overwritten
-int wait_publish_at_least(tgo_ctx* ctx, unsigned long long seq);
 
-// The helpers of the sweeps' per-level path (wait_publish, read_counters, scan_frontier) are
-// inline: a level loop calls nothing across files for them.
+// The helpers of the per-level path (wait_publish, read_counters, the turns, read_words,
+// scan_frontier) are inline: a level loop calls nothing across files for them.
+
+// The host-mapped counter page as words: [0, kCounterWords) what the last publish stored (a Counters,
+// or the words of read_words), then the publish sequence number.
+inline const volatile unsigned long long* host_words(const tgo_ctx* ctx) {
+    return reinterpret_cast<const volatile unsigned long long*>(ctx->sc.hcnt);
+}
 
 // Counters of the work queued so far, without a copy + stream synchronisation: the publish
 // kernel stores them and then a sequence number into host-mapped memory; the host spins on
 // the sequence number (the level loops read a few words per level, so the wake-up latency of
 // a blocking synchronisation dominated short levels).  A stream error ends the spin.
 //
-// Spin on the publish sequence number (a periodic stream query ends the spin on a failure).
-inline int wait_publish(tgo_ctx* ctx, unsigned long long seq) {
-    Scratch& s = ctx->sc;
-    const volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(s.hcnt) + kCounterWords;
-    for (uint64_t it = 1;; ++it) {
-        if (*flag == seq) break;
+// Spin on the publish sequence number (a periodic stream query ends the spin on a failure).  or_later: the
+// wait for a publish that later ones may have overwritten (the words then hold that publish or a later one).
+inline int wait_publish(tgo_ctx* ctx, unsigned long long seq, bool or_later = false) {
+    const volatile unsigned long long* flag = host_words(ctx) + kCounterWords;
+    auto there = [&] { return or_later ? *flag >= seq : *flag == seq; };
+    for (uint64_t it = 1; !there(); ++it) {
         if ((it & 0x3FFF) == 0) {
             const hipError_t q = hipStreamQuery(ctx->stream);
             if (q != hipSuccess && q != hipErrorNotReady) return fail(ctx, TGO_E_HIP, hipGetErrorString(q));
-            if (q == hipSuccess && *flag != seq) return fail(ctx, TGO_E_HIP, "counter publish not visible after the stream drained");
+            if (q == hipSuccess && !there())
+                return fail(ctx, TGO_E_HIP, or_later ? "loop state publish not visible after the stream drained"
+                                                     : "counter publish not visible after the stream drained");
         }
         __builtin_ia32_pause();
     }
@@ -205,6 +186,41 @@ inline int read_counters(tgo_ctx* ctx) {
     const unsigned long long seq = ++s.pub_seq;
     HIP_TRY(k_publish_counters(s.cnt, s.hcnt_dev, seq, ctx->stream));
     return wait_publish(ctx, seq);
+}
+
+// A level turn: the counters are published (with the 64 words of src64, when given, after them) and
+// zero again afterwards, in one launch.  turn_begin queues it and leaves the wait to the caller, who may
+// queue the next level's prefix in between; seq is what wait_publish takes.
+inline int turn_begin(tgo_ctx* ctx, unsigned long long& seq, unsigned long long* src64 = nullptr) {
+    Scratch& s = ctx->sc;
+    seq = ++s.pub_seq;
+    HIP_TRY(k_publish_turn(s.cnt, s.hcnt_dev, seq, src64, ctx->stream));
+    return TGO_OK;
+}
+inline int turn(tgo_ctx* ctx) {
+    unsigned long long seq = 0;
+    if (int rc = turn_begin(ctx, seq)) return rc;
+    return wait_publish(ctx, seq);
+}
+// ... of a program whose kernels set Counters::err when a queue overflows: "<what>: a queue overflowed ..."
+inline int turn_checked(tgo_ctx* ctx, const char* what) {
+    if (int rc = turn(ctx)) return rc;
+    if (ctx->sc.hcnt->err) return fail(ctx, TGO_E_HIP, std::string(what) + ": a queue overflowed (inconsistent lists)");
+    return TGO_OK;
+}
+
+// `count` device words (on the ctx stream, after the work queued so far) to out through the counter
+// page, kCounterWords words a publish: a tiny kernel and a spin instead of a copy and a stream wait.
+inline int read_words(tgo_ctx* ctx, const int64_t* dev, int64_t count, int64_t* out) {
+    Scratch& s = ctx->sc;
+    for (int64_t w0 = 0; w0 < count; w0 += kCounterWords) {
+        const int m = static_cast<int>(std::min<int64_t>(kCounterWords, count - w0));
+        const unsigned long long seq = ++s.pub_seq;
+        HIP_TRY(k_publish_words(dev + w0, m, s.hcnt_dev, seq, ctx->stream));
+        if (int rc = wait_publish(ctx, seq)) return rc;
+        for (int i = 0; i < m; ++i) out[w0 + i] = static_cast<int64_t>(host_words(ctx)[i]);
+    }
+    return TGO_OK;
 }
 
 // Exclusive scan of qdeg[0..qlen) into qpre[0..qlen] (qpre[qlen] = total).
@@ -296,8 +312,18 @@ int fx_take_bad(tgo_ctx* ctx, ColdBlocks& cb, bool* bad);
 int64_t default_delta(const DevGraph& g, bool weighted);
 // The direction-optimizing BFS from internal vertex `seed` (< 0: nobody is reached) along `scope`'s
 // lists: levels in sc.level (-1 unreached), distances in sc.dist, tgo_stats.levels = levels run
-// (the deepest level + 1).  tgo_bfs and tgo_betweenness (api_analytics.cpp) run it.
+// (the deepest level + 1).  tgo_bfs and tgo_betweenness (api_bc.cpp) run it.
 int run_bfs(tgo_ctx* ctx, int64_t seed, int max_depth, int scope);
+
+// ------------------------------------------------------------------ api_cc.cpp
+// g.cc_tid = the Titan id of every internal index, built once per graph: tgo_components, tgo_scc and
+// tgo_peer_pressure label with it.
+int titan_ids_by_index(tgo_ctx* ctx);
+
+// ------------------------------------------------------------------ api_tri.cpp
+// The forward lists and degrees of the simple undirected graph (g.tri_*), built once per graph:
+// tgo_triangles and tgo_kcore walk them.
+int tri_forward_lists(tgo_ctx* ctx);
 
 // ------------------------------------------------------------------ api_msbfs.cpp
 int ms_alloc(tgo_ctx* ctx);
@@ -308,7 +334,7 @@ int64_t ms_head_of(const tgo_ctx* ctx);
 // One sweep of up to 64 sources given as internal ids (all >= 0; ms_alloc done): the level loop of
 // tgo_bfs_multi between its seed resolution and its extraction.  Leaves sc.ms_vis, the level planes
 // [0, sc.ms_nplanes) and sc.ms_nsrc; tgo_stats as tgo_bfs_multi reports them.  tgo_bfs_multi and
-// tgo_closeness (api_analytics.cpp) run it.
+// tgo_closeness (api_cl.cpp) run it.
 int run_ms_sweep(tgo_ctx* ctx, const int64_t* seeds, int32_t nseeds, int32_t max_depth, int32_t scope, int32_t flags);
 
 inline LevelPlanes ms_planes(tgo_ctx* ctx) { return LevelPlanes{ctx->sc.ms_lvl, ctx->g.n}; }

@@ -488,7 +488,7 @@ extern "C" int tgo_part_msbfs_run(tgo_ctx* ctx, tgo_exchange* x, const int64_t* 
     // dense levels: the ghost exchange (only the masks this rank's lists read, lists built once
     // per graph) unless TGO_TUNE_MS_GHOST = 0 or a single rank
     PrGhost* gh = nullptr;
-    if (W > 1 && ctx->ms_ghost != 0) {
+    if (W > 1 && ctx->tune.i64(TGO_TUNE_MS_GHOST) != 0) {
         Driver d{ctx, x, st, dc, hc};
         std::shared_ptr<PrGhost>& cached = ghost_cache(ctx).ms;
         gh = cached.get();

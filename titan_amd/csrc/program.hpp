@@ -5,14 +5,21 @@
 
 namespace tgo {
 
+// Opens a program that takes an args struct A with a scope: the last result is forgotten, a graph is
+// loaded for that scope.  The program's own argument checks follow it.
+template <class A>
+int program_open(tgo_ctx* ctx, const A* a) {
+    if (!ctx) return TGO_E_INVALID;
+    ctx->res_kind = -1;
+    if (!a) return fail(ctx, TGO_E_INVALID, "null args");
+    return check_program(ctx, a->scope);
+}
+
 // Opens an analytic of a bothE load (A: its args struct, named `args`): `runs` is the "<what> <verb>" of
 // its messages, `noun` what an asymmetric neighbour relation leaves undefined (null: it takes one).
 template <class A>
 int bothE_program_check(tgo_ctx* ctx, const A* a, const char* args, const std::string& runs, const char* noun) {
-    if (!ctx) return TGO_E_INVALID;
-    ctx->res_kind = -1;
-    if (!a) return fail(ctx, TGO_E_INVALID, "null args");
-    if (int rc = check_program(ctx, a->scope)) return rc;
+    if (int rc = program_open(ctx, a)) return rc;
     if (a->scope != TGO_SCOPE_BOTH_E)
         return fail(ctx, TGO_E_INVALID, runs + " over bothE; load the graph with TGO_SCOPE_BOTH_E");
     if (a->flags != 0) return fail(ctx, TGO_E_INVALID, std::string(args) + ".flags must be 0");
@@ -22,6 +29,30 @@ int bothE_program_check(tgo_ctx* ctx, const A* a, const char* args, const std::s
                     "the loaded OUT and IN lists are not each other's transpose (tgo_load_csr with asymmetric rows): "
                     "the neighbour relation is asymmetric, " + std::string(noun) + " are not defined on it");
     (void)hipSetDevice(ctx->opts.device);
+    return TGO_OK;
+}
+
+// A seed list (seeds, nseeds): nseeds >= 0 seeds, or -1 for every vertex.
+inline int seed_list_check(tgo_ctx* ctx, const int64_t* seeds, int64_t nseeds) {
+    if (nseeds < -1) return fail(ctx, TGO_E_INVALID, "nseeds must be >= 0, or -1 for every vertex");
+    if (nseeds > 0 && !seeds) return fail(ctx, TGO_E_INVALID, "null seeds");
+    return TGO_OK;
+}
+
+// ... as internal ids in `out`, in the order given (every vertex: in row order).  A Titan id that no
+// executed vertex has is kept as -1 (out[i] is seed i's) or dropped.
+inline int resolve_seeds(tgo_ctx* ctx, const int64_t* seeds, int64_t nseeds, int is_dense, bool keep_unknown,
+                         std::vector<int64_t>& out) {
+    if (int rc = seed_list_check(ctx, seeds, nseeds)) return rc;
+    const int64_t count = nseeds < 0 ? ctx->g.n : nseeds;
+    out.clear();
+    out.reserve(static_cast<size_t>(count));
+    for (int64_t i = 0; i < count; ++i) {
+        int64_t v = -1;
+        if (nseeds < 0) v = ctx->perm[i];
+        else if (int rc = resolve_seed(ctx, seeds[i], is_dense, v)) return rc;
+        if (v >= 0 || keep_unknown) out.push_back(v);
+    }
     return TGO_OK;
 }
 
@@ -81,15 +112,27 @@ inline int last_result_check(tgo_ctx* ctx, int kind, const char* program) {
     return TGO_OK;
 }
 
+// Opens a tgo_copy_* (after its null-pointer checks): the check above, then the device and the queued work.
+inline int copy_open(tgo_ctx* ctx, int kind, const char* program) {
+    if (int rc = last_result_check(ctx, kind, program)) return rc;
+    (void)hipSetDevice(ctx->opts.device);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return TGO_OK;
+}
+
 // All-or-nothing device allocations: what dev_alloc / upload / adopt added since the scope opened is
-// released when it closes without commit() (after a stream wait: queued kernels may still use it).
+// released when it closes without commit() (after a stream wait: queued kernels may still use it);
+// commit() keeps it and counts it in tgo_stats.device_bytes.
 struct AllocScope {
     tgo_ctx* ctx;
     size_t mark;
     int64_t bytes;
     bool committed = false;
     explicit AllocScope(tgo_ctx* c) : ctx(c), mark(c->allocs.size()), bytes(c->dev_bytes) {}
-    void commit() { committed = true; }
+    void commit() {
+        committed = true;
+        ctx->st.device_bytes = ctx->dev_bytes;
+    }
     ~AllocScope() {
         if (committed) return;
         if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
