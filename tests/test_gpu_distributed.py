@@ -366,7 +366,7 @@ def test_edge_balanced_partition_drivers(world, monkeypatch):
 
 @pytest.mark.parametrize("world,fixed,split", [(1, None, -1.0), (2, None, -1.0), (2, 0, -1.0), (4, None, -1.0),
                                                (4, 0, -1.0), (1, None, 0.0), (2, None, 0.3), (4, 0, 0.3),
-                                               (4, None, 0.0)])
+                                               (4, None, 0.0), (1, None, 0.3), (2, 0, 0.3), (4, None, 0.3)])
 def test_native_msbfs_driver(world, fixed, split):
     """tgo_part_msbfs_run: the partitioned multi-source sweep as ONE native call (C++ level
     loop, collectives through an in-process exchange group of thread ranks on this device):

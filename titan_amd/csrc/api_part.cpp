@@ -1,5 +1,7 @@
 // api_part.cpp — the 1-D partitioned (multi-GPU) primitives (include/titan_gpu_olap_part.h): one rank's
 // share of a program's step between two exchanges, and what part_driver.cpp's native loops call.
+// The multi-source steps take what the native sweep chooses per call as arguments (ctx.hpp MsRecv /
+// MsOwn); nothing about one call is kept in the context for the next.
 #include "ctx.hpp"
 
 using namespace tgo;
@@ -287,90 +289,12 @@ int tgo_part_ms_push_masked(tgo_ctx* ctx, const uint64_t* fr_local, uint64_t* ca
     return part_done(ctx);
 }
 
-// The received candidate pairs OR-ed into fr_next (zeroed first), no settle: the pull of the
-// same level reads them (tgo_part_ms_pull_split).
-// With the own-slice bypass on: this rank's candidate words into the owned next masks.
-static hipError_t ms_or_own(tgo_ctx* ctx, uint64_t* fr_next) {
-    if (ctx->part_ms_self < 0 || !ctx->part_ms_cand) return hipSuccess;
-    const int64_t nl = ctx->g.n, cps = (nl + kPackChunk - 1) / kPackChunk;
-    uint8_t* touched = ctx->sc.pk_touch ? ctx->sc.pk_touch + static_cast<int64_t>(ctx->part_ms_self) * cps : nullptr;
-    return k_ms_or_local(ctx->part_ms_cand + static_cast<int64_t>(ctx->part_ms_self) * nl, nl, cps, touched, fr_next,
-                         ctx->stream);
-}
+}  // extern "C" (the step forms tgo_part_msbfs_run calls, ctx.hpp; their C entry points follow)
+namespace tgo {
 
-int tgo_part_ms_or_fixed(tgo_ctx* ctx, const int64_t* recv, int32_t nslices, int64_t cap, uint64_t* fr_next) {
+int part_ms_push(tgo_ctx* ctx, const uint64_t* fr_local, uint64_t* cand_global, uint64_t* own_next, int self) {
     int rc = part_check(ctx);
     if (rc) return rc;
-    if (!recv || !fr_next || nslices < 1 || nslices > kMaxRanks || cap < 1 || cap > ctx->g.n)
-        return fail(ctx, TGO_E_INVALID, "ms_or_fixed: bad arguments");
-    HIP_TRY(hipMemsetAsync(fr_next, 0, ctx->g.n_active * 8, ctx->stream));
-    HIP_TRY(k_ms_or_fixed(recv, nslices, cap, fr_next, ctx->stream));
-    HIP_TRY(ms_or_own(ctx, fr_next));
-    return part_done(ctx);
-}
-
-int tgo_part_ms_or_pairs(tgo_ctx* ctx, const int64_t* recv, const int64_t* recv_counts, int32_t nslices,
-                         uint64_t* fr_next) {
-    int rc = part_check(ctx);
-    if (rc) return rc;
-    if (!recv || !recv_counts || !fr_next || nslices < 1 || nslices > kMaxRanks)
-        return fail(ctx, TGO_E_INVALID, "ms_or_pairs: bad arguments");
-    int64_t npairs = 0;
-    for (int r = 0; r < nslices; ++r) {
-        if (recv_counts[r] < 0 || recv_counts[r] > ctx->g.n) return fail(ctx, TGO_E_INVALID, "ms_or_pairs: bad count");
-        npairs += recv_counts[r];
-    }
-    HIP_TRY(hipMemsetAsync(fr_next, 0, ctx->g.n_active * 8, ctx->stream));
-    HIP_TRY(k_ms_or_pairs(recv, npairs, fr_next, ctx->stream));
-    HIP_TRY(ms_or_own(ctx, fr_next));
-    return part_done(ctx);
-}
-
-int tgo_part_ms_pull_split(tgo_ctx* ctx, int32_t level, const uint64_t* fr_global, uint64_t* fr_next, uint64_t sparse,
-                           int32_t cand_in_next, int64_t* counts) {
-    int rc = part_check(ctx);
-    if (rc) return rc;
-    DevGraph& g = ctx->g;
-    Scratch& s = ctx->sc;
-    hipStream_t st = ctx->stream;
-    const View pull = pull_view(g, TGO_SCOPE_BOTH_E), push = push_view(g, TGO_SCOPE_BOTH_E);
-    const uint64_t full = s.ms_nsrc == 64 ? ~0ULL : ((1ULL << s.ms_nsrc) - 1ULL);
-    if (level + 1 >= (1 << kLevelPlanes)) return fail(ctx, TGO_E_UNSUPPORTED, "multi-source BFS levels are < 65536");
-    if ((rc = ms_planes_for(ctx, level + 1))) return rc;
-    HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), st));
-    const int nxt = ctx->part_cur ^ 1;
-    HIP_TRY(k_ms_pull(pull, push, g.n_active, full, fr_global, nullptr, s.ms_vis, fr_next, ms_planes(ctx), s.cnt,
-                      level + 1, st, 0, full & ~sparse, cand_in_next ? fr_next : nullptr));
-    ctx->part_cur = nxt;
-    ctx->part_queued = false;
-    return part_counts(ctx, counts);
-}
-
-int tgo_part_ms_pull(tgo_ctx* ctx, int32_t level, const uint64_t* fr_global, uint64_t* fr_next, int64_t* counts) {
-    int rc = part_check(ctx);
-    if (rc) return rc;
-    DevGraph& g = ctx->g;
-    Scratch& s = ctx->sc;
-    hipStream_t st = ctx->stream;
-    const View pull = pull_view(g, TGO_SCOPE_BOTH_E), push = push_view(g, TGO_SCOPE_BOTH_E);
-    const uint64_t full = s.ms_nsrc == 64 ? ~0ULL : ((1ULL << s.ms_nsrc) - 1ULL);
-    if (level + 1 >= (1 << kLevelPlanes)) return fail(ctx, TGO_E_UNSUPPORTED, "multi-source BFS levels are < 65536");
-    if ((rc = ms_planes_for(ctx, level + 1))) return rc;
-    HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), st));
-    // the pull writes every active row's mask; the entry-less tail is zero already (no
-    // entry-less seed enters a mask, tgo_part_ms_begin)
-    const int nxt = ctx->part_cur ^ 1;
-    HIP_TRY(k_ms_pull(pull, push, g.n_active, full, fr_global, nullptr, s.ms_vis, fr_next, ms_planes(ctx), s.cnt,
-                      level + 1, st, 0));
-    ctx->part_cur = nxt;
-    ctx->part_queued = false;       // counted only: ms_push builds the queue if it needs one
-    return part_counts(ctx, counts);
-}
-
-int tgo_part_ms_push(tgo_ctx* ctx, int32_t level, const uint64_t* fr_local, uint64_t* cand_global) {
-    int rc = part_check(ctx);
-    if (rc) return rc;
-    (void)level;
     DevGraph& g = ctx->g;
     Scratch& s = ctx->sc;
     int64_t qlen = 0;
@@ -381,17 +305,11 @@ int tgo_part_ms_push(tgo_ctx* ctx, int32_t level, const uint64_t* fr_local, uint
                            ctx->stream));
         ctx->part_queued = true;
     }
-    // bypass on and the next masks named (part_ms_own_next): the owned targets' candidates go
-    // straight into them (zeroed here), so the settle neither zeroes them nor ORs the own slice
-    uint64_t* own = nullptr;
-    int64_t own_lo = 0;
-    if (ctx->part_own_next && ctx->part_ms_self >= 0 && cand_global == ctx->part_ms_cand) {
-        own = ctx->part_own_next;
-        own_lo = static_cast<int64_t>(ctx->part_ms_self) * g.n;
-        HIP_TRY(k_level_prep(nullptr, own, g.n_active, nullptr, ctx->stream));   // the tail stays zero
-    }
-    ctx->part_own_next = nullptr;
-    ctx->part_own_direct = own;
+    // the owned targets' candidates go straight into own_next (zeroed here), so the settle
+    // neither zeroes those masks nor ORs the own slice (MsOwn::direct)
+    uint64_t* own = self >= 0 ? own_next : nullptr;
+    const int64_t own_lo = own ? static_cast<int64_t>(self) * g.n : 0;
+    if (own) HIP_TRY(k_level_prep(nullptr, own, g.n_active, nullptr, ctx->stream));   // the tail stays zero
     if (qlen > 0) {
         if ((rc = scan_frontier(ctx, ctx->part_qlen))) return rc;
         const PackTouch touch{s.pk_touch, g.n, (g.n + kPackChunk - 1) / kPackChunk};
@@ -401,30 +319,195 @@ int tgo_part_ms_push(tgo_ctx* ctx, int32_t level, const uint64_t* fr_local, uint
     return part_done(ctx);
 }
 
-int tgo_part_ms_settle(tgo_ctx* ctx, int32_t level, const uint64_t* recv, int32_t nslices, uint64_t* fr_next,
-                       int64_t* counts) {
+// What the settles and the ORs share: the checks of the received pairs (`name`: the entry
+// point's, for its messages), then the pairs and the rank's own slice OR-ed into fr_next.
+static int ms_recv_check(tgo_ctx* ctx, const char* name, const MsRecv& in, const uint64_t* fr_next, int64_t& npairs) {
+    auto bad = [&](const char* what) {
+        return fail(ctx, TGO_E_INVALID, std::string(name) + (in.sized ? "_pairs: bad " : "_fixed: bad ") + what);
+    };
+    if (!in.recv || !fr_next || in.nslices < 1 || in.nslices > kMaxRanks ||
+        (in.sized ? !in.counts : in.cap < 1 || in.cap > ctx->g.n))
+        return bad("arguments");
+    npairs = 0;
+    for (int r = 0; in.sized && r < in.nslices; ++r) {
+        if (in.counts[r] < 0 || in.counts[r] > ctx->g.n) return bad("count");
+        npairs += in.counts[r];
+    }
+    return TGO_OK;
+}
+
+static int ms_or_received(tgo_ctx* ctx, const MsRecv& in, int64_t npairs, uint64_t* fr_next, const MsOwn& own) {
+    if (in.sized) HIP_TRY(k_ms_or_pairs(in.recv, npairs, fr_next, ctx->stream));
+    else HIP_TRY(k_ms_or_fixed(in.recv, in.nslices, in.cap, fr_next, ctx->stream));
+    if (own.direct || own.self < 0 || !own.cand) return TGO_OK;
+    const int64_t nl = ctx->g.n, cps = (nl + kPackChunk - 1) / kPackChunk;
+    uint8_t* touched = ctx->sc.pk_touch ? ctx->sc.pk_touch + static_cast<int64_t>(own.self) * cps : nullptr;
+    HIP_TRY(k_ms_or_local(own.cand + static_cast<int64_t>(own.self) * nl, nl, cps, touched, fr_next, ctx->stream));
+    return TGO_OK;
+}
+
+// The received candidate pairs OR-ed into fr_next (zeroed first), no settle: the pull of the
+// same level reads them (tgo_part_ms_pull_split).
+int part_ms_or(tgo_ctx* ctx, const MsRecv& in, uint64_t* fr_next, const MsOwn& own) {
+    int rc = part_check(ctx);
+    if (rc) return rc;
+    int64_t npairs = 0;
+    if ((rc = ms_recv_check(ctx, "ms_or", in, fr_next, npairs))) return rc;
+    HIP_TRY(hipMemsetAsync(fr_next, 0, ctx->g.n_active * 8, ctx->stream));
+    if ((rc = ms_or_received(ctx, in, npairs, fr_next, own))) return rc;
+    return part_done(ctx);
+}
+
+// The planes a discovery at level + 1 writes; a sweep is at most 65535 levels deep.
+static int ms_level_planes(tgo_ctx* ctx, int32_t level) {
+    if (level + 1 >= (1 << kLevelPlanes)) return fail(ctx, TGO_E_UNSUPPORTED, "multi-source BFS levels are < 65536");
+    return ms_planes_for(ctx, level + 1);
+}
+
+// The candidates in fr_next settled: the bits not visited yet become level + 1 and the next
+// frontier, queued in the other queue buffer (count_only: counted only), and the level's counts.
+static int ms_settle_tail(tgo_ctx* ctx, int32_t level, uint64_t* fr_next, int64_t* sums, bool count_only, int64_t* counts) {
+    DevGraph& g = ctx->g;
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    unsigned long long* srcent = reinterpret_cast<unsigned long long*>(sums);
+    const int nxt = ctx->part_cur ^ 1;
+    if (count_only) {
+        HIP_TRY(k_ms_settle_count(push_view(g, TGO_SCOPE_BOTH_E), g.n_active, s.ms_vis, fr_next, ms_planes(ctx), s.cnt,
+                                  level + 1, st, srcent));
+    } else {
+        HIP_TRY(k_ms_settle(push_view(g, TGO_SCOPE_BOTH_E), g.n_active, s.ms_vis, fr_next, ms_planes(ctx), s.q[nxt], s.qdeg,
+                            s.cnt, level + 1, st, srcent));
+    }
+    ctx->part_queued = !count_only;
+    ctx->part_cur = nxt;
+    return part_counts(ctx, counts);
+}
+
+int part_ms_settle(tgo_ctx* ctx, int32_t level, const MsRecv& in, uint64_t* fr_next, const MsOwn& own, int64_t* counts) {
+    int rc = part_check(ctx);
+    if (rc) return rc;
+    int64_t npairs = 0;
+    if ((rc = ms_recv_check(ctx, "ms_settle", in, fr_next, npairs)) || (rc = ms_level_planes(ctx, level))) return rc;
+    HIP_TRY(k_level_prep(ctx->sc.cnt, own.direct ? nullptr : fr_next, own.direct ? 0 : ctx->g.n_active, nullptr,
+                         ctx->stream));   // tail stays zero
+    if ((rc = ms_or_received(ctx, in, npairs, fr_next, own))) return rc;
+    return ms_settle_tail(ctx, level, fr_next, own.sums, own.count_only, counts);
+}
+
+// The head of the three packs: the count pass over the candidate masks (slice `self` skipped)
+// and the scan of the chunk counts into pk_off.  cps: chunks per slice.
+static int ms_pack_head(tgo_ctx* ctx, uint64_t* cand_global, int32_t nranks, int64_t* send, int self, int64_t& cps,
+                        int64_t& nchunks) {
+    DevGraph& g = ctx->g;
+    Scratch& s = ctx->sc;
+    hipStream_t st = ctx->stream;
+    cps = (g.n + kPackChunk - 1) / kPackChunk;
+    nchunks = cps * nranks;
+    if (!s.pk_cnt) {
+        HIP_TRY(dev_alloc(ctx, s.pk_cnt, g.n_global / kPackChunk + kMaxRanks + 1));
+        HIP_TRY(dev_alloc(ctx, s.pk_off, g.n_global / kPackChunk + kMaxRanks + 1));
+    }
+    HIP_TRY(hipMemsetAsync(s.pk_cnt + nchunks, 0, sizeof(int64_t), st));
+    HIP_TRY(k_ms_pack(false, cand_global, g.n, cps, nchunks, s.pk_cnt, s.pk_off, send, st, s.pk_touch, self));
+    HIP_TRY(scan_exclusive_i64(s.cub_tmp, s.cub_bytes, s.pk_cnt, s.pk_off, nchunks + 1, st));
+    return TGO_OK;
+}
+
+// Device form of tgo_part_ms_pack: no host synchronisation — the split sizes (int64
+// elements, 2 per pair) go to send_elems_dev for the caller's device all-to-all.
+int part_ms_pack_dev(tgo_ctx* ctx, uint64_t* cand_global, int32_t nranks, int64_t* send, int64_t* send_elems_dev, int self) {
+    int rc = part_check(ctx);
+    if (rc) return rc;
+    DevGraph& g = ctx->g;
+    Scratch& s = ctx->sc;
+    if (!cand_global || !send || !send_elems_dev || nranks < 1 || nranks > kMaxRanks ||
+        static_cast<int64_t>(nranks) * g.n != g.n_global)
+        return fail(ctx, TGO_E_INVALID, "ms_pack_dev: bad arguments (nranks * n_local must equal n_global)");
+    hipStream_t st = ctx->stream;
+    int64_t cps = 0, nchunks = 0;
+    if ((rc = ms_pack_head(ctx, cand_global, nranks, send, self, cps, nchunks))) return rc;
+    HIP_TRY(k_slice_elems(s.pk_off, cps, nranks, send_elems_dev, st));
+    HIP_TRY(k_ms_pack(true, cand_global, g.n, cps, nchunks, s.pk_cnt, s.pk_off, send, st, s.pk_touch, self));
+    return part_done(ctx);
+}
+
+// Fixed-capacity sparse exchange (msbfs.hip ms_pack_fixed): owner r's slot of `send` is
+// 2 * (cap + 1) int64 (header + pairs), so the caller's all-to-all has equal splits.
+int part_ms_pack_fixed(tgo_ctx* ctx, uint64_t* cand_global, int32_t nranks, int64_t cap, int64_t* send, int self) {
+    int rc = part_check(ctx);
+    if (rc) return rc;
+    DevGraph& g = ctx->g;
+    Scratch& s = ctx->sc;
+    if (!cand_global || !send || nranks < 1 || nranks > kMaxRanks || cap < 1 || cap > g.n ||
+        static_cast<int64_t>(nranks) * g.n != g.n_global)
+        return fail(ctx, TGO_E_INVALID, "ms_pack_fixed: bad arguments (1 <= cap <= n_local, nranks * n_local == n_global)");
+    if (!s.pk_ovf) return fail(ctx, TGO_E_STATE, "ms_pack_fixed before ms_begin");
+    int64_t cps = 0, nchunks = 0;
+    if ((rc = ms_pack_head(ctx, cand_global, nranks, send, self, cps, nchunks))) return rc;
+    HIP_TRY(k_ms_pack_fixed(cand_global, g.n, cps, nchunks, s.pk_off, nranks, cap, send, s.pk_ovf, s.pk_touch, ctx->stream,
+                            self));
+    return part_done(ctx);
+}
+
+}  // namespace tgo
+extern "C" {
+
+int tgo_part_ms_or_fixed(tgo_ctx* ctx, const int64_t* recv, int32_t nslices, int64_t cap, uint64_t* fr_next) {
+    return part_ms_or(ctx, MsRecv::fixed(recv, nslices, cap), fr_next, MsOwn{});
+}
+
+int tgo_part_ms_or_pairs(tgo_ctx* ctx, const int64_t* recv, const int64_t* recv_counts, int32_t nslices,
+                         uint64_t* fr_next) {
+    return part_ms_or(ctx, MsRecv::pairs(recv, recv_counts, nslices), fr_next, MsOwn{});
+}
+
+// One pull level over the gathered frontier masks.  sparse (null: none): the sources a split
+// level pushed instead — they stay out of the pull, and with cand_in_next their candidates are
+// in fr_next already (tgo_part_ms_or_*).
+static int ms_pull(tgo_ctx* ctx, int32_t level, const uint64_t* fr_global, uint64_t* fr_next, const uint64_t* sparse,
+                   int32_t cand_in_next, int64_t* counts) {
     int rc = part_check(ctx);
     if (rc) return rc;
     DevGraph& g = ctx->g;
     Scratch& s = ctx->sc;
     hipStream_t st = ctx->stream;
-    if (level + 1 >= (1 << kLevelPlanes)) return fail(ctx, TGO_E_UNSUPPORTED, "multi-source BFS levels are < 65536");
-    if ((rc = ms_planes_for(ctx, level + 1))) return rc;
+    const View pull = pull_view(g, TGO_SCOPE_BOTH_E), push = push_view(g, TGO_SCOPE_BOTH_E);
+    const uint64_t full = s.ms_nsrc == 64 ? ~0ULL : ((1ULL << s.ms_nsrc) - 1ULL);
+    if ((rc = ms_level_planes(ctx, level))) return rc;
     HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), st));
-    HIP_TRY(k_or_slices(recv, nslices, g.n, fr_next, st));
+    // the pull writes every active row's mask; the entry-less tail is zero already (no
+    // entry-less seed enters a mask, tgo_part_ms_begin)
     const int nxt = ctx->part_cur ^ 1;
-    if (ctx->part_count_only) {
-        HIP_TRY(k_ms_settle_count(push_view(g, TGO_SCOPE_BOTH_E), g.n_active, s.ms_vis, fr_next, ms_planes(ctx), s.cnt,
-                                  level + 1, st, ctx->part_srcent));
-    } else {
-        HIP_TRY(k_ms_settle(push_view(g, TGO_SCOPE_BOTH_E), g.n_active, s.ms_vis, fr_next, ms_planes(ctx), s.q[nxt], s.qdeg,
-                            s.cnt, level + 1, st, ctx->part_srcent));
-    }
-    ctx->part_queued = !ctx->part_count_only;
-    ctx->part_srcent = nullptr;
-    ctx->part_count_only = false;
+    HIP_TRY(k_ms_pull(pull, push, g.n_active, full, fr_global, nullptr, s.ms_vis, fr_next, ms_planes(ctx), s.cnt,
+                      level + 1, st, 0, sparse ? full & ~*sparse : ~0ULL, cand_in_next ? fr_next : nullptr));
     ctx->part_cur = nxt;
+    ctx->part_queued = false;       // counted only: ms_push builds the queue if it needs one
     return part_counts(ctx, counts);
+}
+
+int tgo_part_ms_pull_split(tgo_ctx* ctx, int32_t level, const uint64_t* fr_global, uint64_t* fr_next, uint64_t sparse,
+                           int32_t cand_in_next, int64_t* counts) {
+    return ms_pull(ctx, level, fr_global, fr_next, &sparse, cand_in_next, counts);
+}
+
+int tgo_part_ms_pull(tgo_ctx* ctx, int32_t level, const uint64_t* fr_global, uint64_t* fr_next, int64_t* counts) {
+    return ms_pull(ctx, level, fr_global, fr_next, nullptr, 0, counts);
+}
+
+int tgo_part_ms_push(tgo_ctx* ctx, int32_t level, const uint64_t* fr_local, uint64_t* cand_global) {
+    (void)level;
+    return part_ms_push(ctx, fr_local, cand_global, nullptr, -1);
+}
+
+int tgo_part_ms_settle(tgo_ctx* ctx, int32_t level, const uint64_t* recv, int32_t nslices, uint64_t* fr_next,
+                       int64_t* counts) {
+    int rc = part_check(ctx);
+    if (rc) return rc;
+    if ((rc = ms_level_planes(ctx, level))) return rc;
+    HIP_TRY(hipMemsetAsync(ctx->sc.cnt, 0, sizeof(Counters), ctx->stream));
+    HIP_TRY(k_or_slices(recv, nslices, ctx->g.n, fr_next, ctx->stream));
+    return ms_settle_tail(ctx, level, fr_next, nullptr, false, counts);
 }
 
 int tgo_part_ms_pack(tgo_ctx* ctx, uint64_t* cand_global, int32_t nranks, int64_t* send, int64_t* send_counts) {
@@ -436,15 +519,8 @@ int tgo_part_ms_pack(tgo_ctx* ctx, uint64_t* cand_global, int32_t nranks, int64_
         static_cast<int64_t>(nranks) * g.n != g.n_global)
         return fail(ctx, TGO_E_INVALID, "ms_pack: bad arguments (nranks * n_local must equal n_global)");
     hipStream_t st = ctx->stream;
-    const int64_t cps = (g.n + kPackChunk - 1) / kPackChunk;     // chunks per slice
-    const int64_t nchunks = cps * nranks;
-    if (!s.pk_cnt) {
-        HIP_TRY(dev_alloc(ctx, s.pk_cnt, g.n_global / kPackChunk + kMaxRanks + 1));
-        HIP_TRY(dev_alloc(ctx, s.pk_off, g.n_global / kPackChunk + kMaxRanks + 1));
-    }
-    HIP_TRY(hipMemsetAsync(s.pk_cnt + nchunks, 0, sizeof(int64_t), st));
-    HIP_TRY(k_ms_pack(false, cand_global, g.n, cps, nchunks, s.pk_cnt, s.pk_off, send, st, s.pk_touch));
-    HIP_TRY(scan_exclusive_i64(s.cub_tmp, s.cub_bytes, s.pk_cnt, s.pk_off, nchunks + 1, st));
+    int64_t cps = 0, nchunks = 0;
+    if ((rc = ms_pack_head(ctx, cand_global, nranks, send, -1, cps, nchunks))) return rc;
     std::vector<int64_t> off(nranks + 1);
     for (int r = 0; r <= nranks; ++r)     // offsets at the slice boundaries (pk_cnt[nchunks] is 0)
         HIP_TRY(hipMemcpyAsync(&off[r], s.pk_off + r * cps, sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -454,124 +530,22 @@ int tgo_part_ms_pack(tgo_ctx* ctx, uint64_t* cand_global, int32_t nranks, int64_
     return part_done(ctx);
 }
 
-// Device form of tgo_part_ms_pack: no host synchronisation — the split sizes (int64
-// elements, 2 per pair) go to send_elems_dev for the caller's device all-to-all.
 int tgo_part_ms_pack_dev(tgo_ctx* ctx, uint64_t* cand_global, int32_t nranks, int64_t* send, int64_t* send_elems_dev) {
-    int rc = part_check(ctx);
-    if (rc) return rc;
-    DevGraph& g = ctx->g;
-    Scratch& s = ctx->sc;
-    if (!cand_global || !send || !send_elems_dev || nranks < 1 || nranks > kMaxRanks ||
-        static_cast<int64_t>(nranks) * g.n != g.n_global)
-        return fail(ctx, TGO_E_INVALID, "ms_pack_dev: bad arguments (nranks * n_local must equal n_global)");
-    hipStream_t st = ctx->stream;
-    const int64_t cps = (g.n + kPackChunk - 1) / kPackChunk;
-    const int64_t nchunks = cps * nranks;
-    if (!s.pk_cnt) {
-        HIP_TRY(dev_alloc(ctx, s.pk_cnt, g.n_global / kPackChunk + kMaxRanks + 1));
-        HIP_TRY(dev_alloc(ctx, s.pk_off, g.n_global / kPackChunk + kMaxRanks + 1));
-    }
-    const int self = cand_global == ctx->part_ms_cand ? ctx->part_ms_self : -1;
-    HIP_TRY(hipMemsetAsync(s.pk_cnt + nchunks, 0, sizeof(int64_t), st));
-    HIP_TRY(k_ms_pack(false, cand_global, g.n, cps, nchunks, s.pk_cnt, s.pk_off, send, st, s.pk_touch, self));
-    HIP_TRY(scan_exclusive_i64(s.cub_tmp, s.cub_bytes, s.pk_cnt, s.pk_off, nchunks + 1, st));
-    HIP_TRY(k_slice_elems(s.pk_off, cps, nranks, send_elems_dev, st));
-    HIP_TRY(k_ms_pack(true, cand_global, g.n, cps, nchunks, s.pk_cnt, s.pk_off, send, st, s.pk_touch, self));
-    return part_done(ctx);
+    return part_ms_pack_dev(ctx, cand_global, nranks, send, send_elems_dev, -1);
 }
 
-// Fixed-capacity sparse exchange (msbfs.hip ms_pack_fixed): owner r's slot of `send` is
-// 2 * (cap + 1) int64 (header + pairs), so the caller's all-to-all has equal splits.
 int tgo_part_ms_pack_fixed(tgo_ctx* ctx, uint64_t* cand_global, int32_t nranks, int64_t cap, int64_t* send) {
-    int rc = part_check(ctx);
-    if (rc) return rc;
-    DevGraph& g = ctx->g;
-    Scratch& s = ctx->sc;
-    if (!cand_global || !send || nranks < 1 || nranks > kMaxRanks || cap < 1 || cap > g.n ||
-        static_cast<int64_t>(nranks) * g.n != g.n_global)
-        return fail(ctx, TGO_E_INVALID, "ms_pack_fixed: bad arguments (1 <= cap <= n_local, nranks * n_local == n_global)");
-    if (!s.pk_ovf) return fail(ctx, TGO_E_STATE, "ms_pack_fixed before ms_begin");
-    hipStream_t st = ctx->stream;
-    const int64_t cps = (g.n + kPackChunk - 1) / kPackChunk;
-    const int64_t nchunks = cps * nranks;
-    if (!s.pk_cnt) {
-        HIP_TRY(dev_alloc(ctx, s.pk_cnt, g.n_global / kPackChunk + kMaxRanks + 1));
-        HIP_TRY(dev_alloc(ctx, s.pk_off, g.n_global / kPackChunk + kMaxRanks + 1));
-    }
-    const int self = cand_global == ctx->part_ms_cand ? ctx->part_ms_self : -1;
-    HIP_TRY(hipMemsetAsync(s.pk_cnt + nchunks, 0, sizeof(int64_t), st));
-    HIP_TRY(k_ms_pack(false, cand_global, g.n, cps, nchunks, s.pk_cnt, s.pk_off, send, st, s.pk_touch, self));
-    HIP_TRY(scan_exclusive_i64(s.cub_tmp, s.cub_bytes, s.pk_cnt, s.pk_off, nchunks + 1, st));
-    HIP_TRY(k_ms_pack_fixed(cand_global, g.n, cps, nchunks, s.pk_off, nranks, cap, send, s.pk_ovf, s.pk_touch, st,
-                            self));
-    return part_done(ctx);
+    return part_ms_pack_fixed(ctx, cand_global, nranks, cap, send, -1);
 }
 
 int tgo_part_ms_settle_fixed(tgo_ctx* ctx, int32_t level, const int64_t* recv, int32_t nslices, int64_t cap,
                              uint64_t* fr_next, int64_t* counts) {
-    int rc = part_check(ctx);
-    if (rc) return rc;
-    DevGraph& g = ctx->g;
-    Scratch& s = ctx->sc;
-    hipStream_t st = ctx->stream;
-    if (!recv || !fr_next || nslices < 1 || nslices > kMaxRanks || cap < 1 || cap > g.n)
-        return fail(ctx, TGO_E_INVALID, "ms_settle_fixed: bad arguments");
-    if (level + 1 >= (1 << kLevelPlanes)) return fail(ctx, TGO_E_UNSUPPORTED, "multi-source BFS levels are < 65536");
-    if ((rc = ms_planes_for(ctx, level + 1))) return rc;
-    const bool direct = ctx->part_own_direct == fr_next;     // the push wrote the owned targets here
-    ctx->part_own_direct = nullptr;
-    HIP_TRY(k_level_prep(s.cnt, direct ? nullptr : fr_next, direct ? 0 : g.n_active, nullptr, st));   // tail stays zero
-    HIP_TRY(k_ms_or_fixed(recv, nslices, cap, fr_next, st));
-    if (!direct) HIP_TRY(ms_or_own(ctx, fr_next));
-    const int nxt = ctx->part_cur ^ 1;
-    if (ctx->part_count_only) {
-        HIP_TRY(k_ms_settle_count(push_view(g, TGO_SCOPE_BOTH_E), g.n_active, s.ms_vis, fr_next, ms_planes(ctx), s.cnt,
-                                  level + 1, st, ctx->part_srcent));
-    } else {
-        HIP_TRY(k_ms_settle(push_view(g, TGO_SCOPE_BOTH_E), g.n_active, s.ms_vis, fr_next, ms_planes(ctx), s.q[nxt], s.qdeg,
-                            s.cnt, level + 1, st, ctx->part_srcent));
-    }
-    ctx->part_queued = !ctx->part_count_only;
-    ctx->part_srcent = nullptr;
-    ctx->part_count_only = false;
-    ctx->part_cur = nxt;
-    return part_counts(ctx, counts);
+    return part_ms_settle(ctx, level, MsRecv::fixed(recv, nslices, cap), fr_next, MsOwn{}, counts);
 }
 
 int tgo_part_ms_settle_pairs(tgo_ctx* ctx, int32_t level, const int64_t* recv, const int64_t* recv_counts,
                              int32_t nslices, uint64_t* fr_next, int64_t* counts) {
-    int rc = part_check(ctx);
-    if (rc) return rc;
-    DevGraph& g = ctx->g;
-    Scratch& s = ctx->sc;
-    hipStream_t st = ctx->stream;
-    if (!recv || !recv_counts || !fr_next || nslices < 1 || nslices > kMaxRanks)
-        return fail(ctx, TGO_E_INVALID, "ms_settle_pairs: bad arguments");
-    if (level + 1 >= (1 << kLevelPlanes)) return fail(ctx, TGO_E_UNSUPPORTED, "multi-source BFS levels are < 65536");
-    if ((rc = ms_planes_for(ctx, level + 1))) return rc;
-    const bool direct = ctx->part_own_direct == fr_next;     // the push wrote the owned targets here
-    ctx->part_own_direct = nullptr;
-    HIP_TRY(k_level_prep(s.cnt, direct ? nullptr : fr_next, direct ? 0 : g.n_active, nullptr, st));   // tail stays zero
-    int64_t npairs = 0;
-    for (int r = 0; r < nslices; ++r) {
-        if (recv_counts[r] < 0 || recv_counts[r] > g.n) return fail(ctx, TGO_E_INVALID, "ms_settle_pairs: bad count");
-        npairs += recv_counts[r];
-    }
-    HIP_TRY(k_ms_or_pairs(recv, npairs, fr_next, st));
-    if (!direct) HIP_TRY(ms_or_own(ctx, fr_next));
-    const int nxt = ctx->part_cur ^ 1;
-    if (ctx->part_count_only) {
-        HIP_TRY(k_ms_settle_count(push_view(g, TGO_SCOPE_BOTH_E), g.n_active, s.ms_vis, fr_next, ms_planes(ctx), s.cnt,
-                                  level + 1, st, ctx->part_srcent));
-    } else {
-        HIP_TRY(k_ms_settle(push_view(g, TGO_SCOPE_BOTH_E), g.n_active, s.ms_vis, fr_next, ms_planes(ctx), s.q[nxt], s.qdeg,
-                            s.cnt, level + 1, st, ctx->part_srcent));
-    }
-    ctx->part_queued = !ctx->part_count_only;
-    ctx->part_srcent = nullptr;
-    ctx->part_count_only = false;
-    ctx->part_cur = nxt;
-    return part_counts(ctx, counts);
+    return part_ms_settle(ctx, level, MsRecv::pairs(recv, recv_counts, nslices), fr_next, MsOwn{}, counts);
 }
 
 int tgo_part_ms_end(tgo_ctx* ctx, int64_t* reached, int64_t* entries) {
@@ -1166,29 +1140,6 @@ int part_read_words(tgo_ctx* ctx, const int64_t* dev, int count, int64_t* out) {
     if (!ctx->sc.hcnt || count < 0 || count > kCounterWords) return fail(ctx, TGO_E_STATE, "part_read_words");
     return read_words(ctx, dev, count, out);
 }
-// The next multi-source settle also sums the new frontier's push entries per source into
-// out (64 words, zeroed here on the ctx stream): the native driver's split after that level
-// reads them instead of a tgo_part_ms_source_entries pass.  One-shot; nullptr cancels.
-// count_only: that settle builds no frontier queue (the next level will likely pull;
-// tgo_part_ms_push builds the queue if it runs after all).
-int part_ms_settle_sums(tgo_ctx* ctx, int64_t* out, bool count_only) {
-    ctx->part_srcent = nullptr;                                  // out == nullptr: cancel
-    ctx->part_count_only = count_only;
-    if (!out) return TGO_OK;
-    HIP_TRY(hipMemsetAsync(out, 0, 64 * sizeof(int64_t), ctx->stream));
-    ctx->part_srcent = reinterpret_cast<unsigned long long*>(out);
-    return TGO_OK;
-}
-// The next tgo_part_ms_push writes its owned targets' candidates straight into next (with the
-// bypass on); nullptr cancels.
-void part_ms_own_next(tgo_ctx* ctx, uint64_t* next) {
-    ctx->part_own_next = next;
-    if (!next) ctx->part_own_direct = nullptr;
-}
-void part_ms_bypass(tgo_ctx* ctx, uint64_t* cand_global, int self) {
-    ctx->part_ms_cand = cand_global;
-    ctx->part_ms_self = cand_global ? self : -1;
-}
 int part_in_list(tgo_ctx* ctx, const int32_t** adj, int64_t* nnz) {
     if (int rc = part_check(ctx)) return rc;
     *adj = ctx->g.in.adj;
@@ -1218,7 +1169,7 @@ int part_dims(tgo_ctx* ctx, int64_t* n_local, int64_t* lo, int64_t* n_global, in
     *entries = ctx->g.out.nnz + ctx->g.in.nnz;
     return TGO_OK;
 }
-int part_scratch(tgo_ctx* ctx, void** p, int64_t bytes, int slot) {
+int part_scratch(tgo_ctx* ctx, void** p, int64_t bytes, Scratch::DrvSlot slot) {
     Scratch& s = ctx->sc;
     if (slot < 0 || slot >= Scratch::kDrvSlots) return fail(ctx, TGO_E_INVALID, "driver scratch slot");
     if (s.drv_bytes[slot] < bytes) {                // fresh buffers start zero

@@ -1,5 +1,5 @@
 // ctx.hpp — the context behind the C-ABI's opaque tgo_ctx, and the helpers that the driver
-// files (api*.cpp, part_driver.cpp) share: a function used by more than one of them is declared here,
+// files (api*.cpp, part_driver.cpp, part_load.cpp) share: a function used by more than one of them is declared here,
 // once, under its file's heading; program.hpp (included last) is the frame of a program driver.  Private.
 #pragma once
 #include <algorithm>
@@ -37,10 +37,6 @@ struct tgo_ctx {
     int part_cur = 0;           // partitioned BFS: queue buffer holding the frontier
     int64_t part_qlen = 0;      // its length
     bool part_queued = true;    // q[part_cur] holds the frontier (pull / bottom-up levels only count it)
-    // native multi-source sweep (part_driver.cpp): this rank's slice of the candidate words is
-    // not packed but ORed in directly (tgo::part_ms_bypass); -1 = every slice packed
-    int part_ms_self = -1;
-    uint64_t* part_ms_cand = nullptr;
     const uint64_t* part_frontier = nullptr;   // after bottom-up: the caller's nb_local (queued lazily)
     int64_t* part_dcounts = nullptr;    // caller's device counts (tgo_part_device_counts)
     int64_t* part_qlen_dev = nullptr;   // device copy of the queue length (lazy host read)
@@ -71,10 +67,6 @@ struct tgo_ctx {
     tgo::ResultSource res_src;
     int num_cus = 256;          // compute units of the device (persistent launches)
     tgo::Tuning tune;           // tgo_set_tuning (tuning.hpp): one value per TGO_TUNE_* key
-    unsigned long long* part_srcent = nullptr;   // next settle's per-source sums (part_ms_settle_sums)
-    bool part_count_only = false;               // next settle: no queue (part_ms_settle_sums)
-    uint64_t* part_own_next = nullptr;          // next push: owned targets straight into these masks
-    uint64_t* part_own_direct = nullptr;        // the last push did so (its settle skips the own OR)
     int64_t tri_max = 0;        // largest count of the last tgo_triangles (an Integer key's range check)
     // state a native partitioned driver keeps between runs on this graph (part_driver.cpp:
     // the PageRank ghost lists); dropped with the graph
@@ -271,14 +263,39 @@ inline int part_counts(tgo_ctx* ctx, int64_t* counts, bool device_ok = true) {
 
 // ... and what part_driver.cpp's loops call between them
 int part_dims(tgo_ctx* ctx, int64_t* n_local, int64_t* lo, int64_t* n_global, int64_t* entries);
-int part_scratch(tgo_ctx* ctx, void** p, int64_t bytes, int slot);
-// this rank's slice of the candidate words bypasses the pack / exchange (ORed in directly by the
-// settle); (nullptr, -1) turns it off
-void part_ms_bypass(tgo_ctx* ctx, uint64_t* cand_global, int self);
-// the next settle sums its new frontier's push entries per source into out (one-shot)
-int part_ms_settle_sums(tgo_ctx* ctx, int64_t* out, bool count_only = false);
-// the next push writes its owned targets straight into next (bypass on); nullptr cancels
-void part_ms_own_next(tgo_ctx* ctx, uint64_t* next);
+int part_scratch(tgo_ctx* ctx, void** p, int64_t bytes, Scratch::DrvSlot slot);
+// The multi-source steps as tgo_part_msbfs_run calls them: what the rank's own slice does is an
+// argument of every call.  The C entry points of the same names pass the defaults (self = -1,
+// MsOwn{}): every slice packed, nothing written directly, no sums, a queue built.
+// What a settle / or reads: `nslices` fixed slots of `cap` pairs (tgo_part_ms_pack_fixed's
+// layout), or sized pairs back to back with the host pair counts per slice.
+struct MsRecv {
+    const int64_t* recv;
+    int32_t nslices;
+    int64_t cap;                // fixed slots
+    const int64_t* counts;      // sized pairs
+    bool sized;
+    static MsRecv fixed(const int64_t* recv, int32_t nslices, int64_t cap) { return {recv, nslices, cap, nullptr, false}; }
+    static MsRecv pairs(const int64_t* recv, const int64_t* counts, int32_t nslices) { return {recv, nslices, 0, counts, true}; }
+};
+struct MsOwn {
+    uint64_t* cand = nullptr;   // candidate masks whose slice `self` the pack skipped: ORed into the
+    int self = -1;              // next masks here (and cleared); null / -1: every slice travelled
+    bool direct = false;        // the push wrote the owned targets' candidates into the next masks
+                                // (part_ms_push own_next): they are neither zeroed nor ORed here
+    int64_t* sums = nullptr;    // settle: the new frontier's push entries per source are added to
+                                // these 64 words (the caller zeroes them on the ctx stream)
+    bool count_only = false;    // settle: no frontier queue (the next level will likely pull;
+                                // the next push builds the queue if it runs after all)
+};
+// own_next with self >= 0: the candidates of the targets this rank owns go straight into these
+// next masks (zeroed here) instead of slice `self` of cand_global
+int part_ms_push(tgo_ctx* ctx, const uint64_t* fr_local, uint64_t* cand_global, uint64_t* own_next, int self);
+// self: the slice of cand_global the pack skips (left for MsOwn::cand), -1: none
+int part_ms_pack_dev(tgo_ctx* ctx, uint64_t* cand_global, int32_t nranks, int64_t* send, int64_t* send_elems_dev, int self);
+int part_ms_pack_fixed(tgo_ctx* ctx, uint64_t* cand_global, int32_t nranks, int64_t cap, int64_t* send, int self);
+int part_ms_or(tgo_ctx* ctx, const MsRecv& in, uint64_t* fr_next, const MsOwn& own);
+int part_ms_settle(tgo_ctx* ctx, int32_t level, const MsRecv& in, uint64_t* fr_next, const MsOwn& own, int64_t* counts);
 // device words to the host through the mapped counter page (no stream synchronisation)
 int part_read_words(tgo_ctx* ctx, const int64_t* dev, int count, int64_t* out);
 int part_in_list(tgo_ctx* ctx, const int32_t** adj, int64_t* nnz);

@@ -590,8 +590,17 @@ struct DsLoop {
 
 struct Scratch {
     static constexpr int kDrvSlots = 24;
-    void* drv[kDrvSlots] = {};  // partitioned C++ driver buffers (part_driver.cpp), by slot:
-    int64_t drv_bytes[kDrvSlots] = {};   // 0-7 multi-source sweep, 8-12 BFS, 13-17 SSSP, 18-23 PageRank
+    // The buffers of the partitioned C++ loops (part_driver.cpp), one slot each.  The values are
+    // fixed: the programs that share a context keep their buffers from run to run.  *Words: the
+    // loop's device scalars (driver_open); *GhostSizes: build_ghost's count exchange.
+    enum DrvSlot : int {
+        kMsMask0 = 0, kMsMask1 = 1, kMsCand = 2, kMsSend = 3, kMsRecv = 4, kMsWords = 5, kMsSizes = 6, kMsGhostSizes = 7,
+        kBfsFront0 = 8, kBfsFront1 = 9, kBfsDisc = 10, kBfsRecv = 11, kBfsWords = 12, kBfsCounts = 13,
+        kSsspSend = 14, kSsspRecv = 15, kSsspSizes = 16, kSsspWords = 17,
+        kPrContrib = 18, kPrGathered = 19, kPrGhostSizes = 21, kPrWords = 22,
+    };
+    void* drv[kDrvSlots] = {};
+    int64_t drv_bytes[kDrvSlots] = {};
     int64_t n = 0;
     int32_t* level = nullptr;       // n
     int32_t* q[2] = {nullptr, nullptr};   // frontier queues
