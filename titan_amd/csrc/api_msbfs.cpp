@@ -17,6 +17,14 @@ int ms_alloc(tgo_ctx* ctx) {
     HIP_TRY(dev_alloc(ctx, s.ms_fr, n + 1));
     HIP_TRY(dev_alloc(ctx, s.ms_nx, n + 1));
     HIP_TRY(dev_alloc(ctx, s.ms_lvl, n * kLevelPlanes + 1));
+    // the entry-less rows of every plane, once: no level writes them (record_level sees rows with
+    // entries only) and the readers (ms_extract, the closeness fold) take them under vis, so the
+    // sweeps fill [0, n_active) only
+    s.ms_clean = 0;
+    if (n > ctx->g.n_active)
+        for (int k = 0; k < kLevelPlanes; ++k)
+            HIP_TRY(hipMemsetAsync(s.ms_lvl + static_cast<int64_t>(k) * n + ctx->g.n_active, 0,
+                                   (n - ctx->g.n_active) * sizeof(uint64_t), ctx->stream));
     HIP_TRY(dev_alloc(ctx, s.ms_fbm, (n + 63) / 64 + 1));
     HIP_TRY(dev_alloc(ctx, s.ms_seeds, TGO_MAX_SOURCES));
     HIP_TRY(dev_alloc(ctx, s.ms_stat, 2 * TGO_MAX_SOURCES));
@@ -141,6 +149,16 @@ int run_ms_sweep(tgo_ctx* ctx, const int64_t* in, int32_t nseeds, int32_t max_de
     // TGO_TUNE_MS_HEAD: the entries of its own lists a lane with a long list probes before the
     // whole wave takes the list (0 = off)
     const int64_t head = tgo::ms_head_of(ctx);
+    // TGO_MS_COMPACT (default on, 0 = off): the pull levels that count mu — the level after the
+    // frontier's peak and every stay-rule level after it — run ms_pull_compact; TGO_MS_CHUNK: the
+    // vertices a wave scans before it walks the open ones (512 / 1024 / 2048).  Not with the
+    // diagnostic tallies (TGO_MS_DIAG), which the word form keeps.
+    static const bool diag = env_double("TGO_MS_DIAG", 0.0) != 0.0;
+    static const bool compact_on = env_i64("TGO_MS_COMPACT", 1) != 0 && !diag;
+    static const int32_t compact_chunk = [] {
+        const int64_t c = env_i64("TGO_MS_CHUNK", kMsChunkDefault);
+        return static_cast<int32_t>(c == 512 || c == 1024 || c == 2048 ? c : kMsChunkDefault);
+    }();
     int64_t qlen = static_cast<int64_t>(uniq.size());
     int64_t mf = 0;             // the seeds' entries are not read back: level 0 always pushes (a
                                 // direction is policy only; the read cost a stream drain, ~45 us)
@@ -168,8 +186,12 @@ int run_ms_sweep(tgo_ctx* ctx, const int64_t* in, int32_t nseeds, int32_t max_de
         const bool stay = pulled && mu >= 0 && stay_gamma > 0.0 &&
                           static_cast<double>(mu) <= stay_gamma * static_cast<double>(mf);
         const bool use_pull = stay || static_cast<double>(mf) * ms_alpha > static_cast<double>(total);
-        DevSpan span(st, "msbfs.level", {"level", L}, {"pull", use_pull ? 1 : 0});
-        if ((rc = ms_planes_for(ctx, L + 1))) return rc;
+        DevSpan span(st, "msbfs.level", {"level", L}, {"pull", use_pull ? 1 : 0}, {"compact", 0});
+        if ((rc = ms_planes_for(ctx, L + 1, true))) return rc;
+        // this level writes the planes of L + 1's set bits: not clean while it runs (a failed or
+        // depth-cut sweep leaves them so); clean again if it turns out to have found nothing
+        const uint32_t was_clean = s.ms_clean & ms_planes_written(L + 1);
+        s.ms_clean &= ~was_clean;
         const bool queued_before = queued;
         if (!use_pull && !queued) {     // the frontier's queue, for the push level's scan
             if (!cnt_zero) HIP_TRY(hipMemsetAsync(s.cnt, 0, sizeof(Counters), st));
@@ -273,9 +295,14 @@ int run_ms_sweep(tgo_ctx* ctx, const int64_t* in, int32_t nseeds, int32_t max_de
             // threshold: the count is one more atomic per block, 9 - 25 us at RMAT-24's two
             // large levels.
             count_open = stay_gamma > 0.0 && !cs.acc && mf < prev_mf;
+            // ... and where it counts mu it runs compact: past the peak few vertices are open (a
+            // source-split level stays on the word form, which takes the split's candidates)
+            const bool compact = compact_on && count_open && !sparse;
+            if (compact) span.set_third(1);
             HIP_TRY(k_ms_pull(pull, push, g.n_active, full, fr, filter ? s.ms_fbm : nullptr, s.ms_vis, nx,
                               ms_planes(ctx), s.cnt, L + 1, st, filter ? filter_from : 0, full & ~sparse,
-                              sparse ? nx : nullptr, cs, count_open, cs.acc ? 0 : head));   // hot_lim's cut rule as it was
+                              sparse ? nx : nullptr, cs, count_open, cs.acc ? 0 : head,    // hot_lim's cut rule as it was
+                              compact ? compact_chunk : 0));
             if (cs.acc) {
                 HIP_TRY(k_ms_cold(g.msc_adj, g.msc_row, g.msc_C, fr, s.ms_need, s.ms_cacc, st));
                 HIP_TRY(k_ms_finish(push, g.n_active, full, s.ms_vis, nx, sparse ? nx : nullptr, ms_planes(ctx), s.cnt,
@@ -352,10 +379,11 @@ int run_ms_sweep(tgo_ctx* ctx, const int64_t* in, int32_t nseeds, int32_t max_de
             if ((rc = turn_begin(ctx, seq, sums ? s.ms_srcent : nullptr))) return rc;
             cnt_zero = true;
             if (sums) s.ms_srcent_zero = true;
-            if (L + 1 < depth && (rc = ms_planes_for(ctx, L + 2))) return rc;
+            if (L + 1 < depth && (rc = ms_planes_for(ctx, L + 2, true))) return rc;
             if ((rc = wait_publish(ctx, seq))) return rc;
         }
         qlen = static_cast<int64_t>(s.hcnt->qlen);
+        if (qlen == 0) s.ms_clean |= was_clean;      // nothing found: nothing recorded
         prev_mf = mf;
         mf = static_cast<int64_t>(s.hcnt->mf);
         mu = count_open ? static_cast<int64_t>(s.hcnt->open) : -1;
@@ -370,7 +398,6 @@ int run_ms_sweep(tgo_ctx* ctx, const int64_t* in, int32_t nseeds, int32_t max_de
                                 use_pull ? "pull" : "push", (long long)qlen, (long long)mf, s.hcnt->red[0],
                                 use_pull ? (stay ? " (stayed in pull)" : "") : (sparse_level ? " (sparse)" : ""));
         if (trace && count_open) std::fprintf(stderr, "[tgo]   %lld list entries of still-open vertices\n", (long long)mu);
-        static const bool diag = env_double("TGO_MS_DIAG", 0.0) != 0.0;
         if (trace && diag && use_pull) {
             unsigned long long d[kMsDiagWords] = {};
             HIP_TRY(k_ms_diag_take(d, st));

@@ -359,15 +359,32 @@ inline LevelPlanes ms_planes(tgo_ctx* ctx) { return LevelPlanes{ctx->sc.ms_lvl, 
 // Zero the level planes a discovery at `level` writes (planes 0..floor(log2(level))) that
 // this sweep has not zeroed yet: vertices reached earlier have levels < 2^k, whose bit k
 // is 0, so a plane is valid from the moment it is zeroed.
-inline int ms_planes_for(tgo_ctx* ctx, int32_t level) {
+// keep_clean (the one-GPU sweep): only the rows a level can write, [0, n_active) — the rest is zero
+// since ms_alloc — and not at all a plane that sc.ms_clean knows to be zero still (filled by an
+// earlier sweep for a level that then found nothing).  The caller takes a plane's bit down
+// before it launches a level that writes the plane (ms_planes_written).  Without keep_clean (the
+// partitioned sweep, which does not track its writes) the whole plane is filled and its bit dropped.
+inline int ms_planes_for(tgo_ctx* ctx, int32_t level, bool keep_clean = false) {
     Scratch& s = ctx->sc;
     while (s.ms_nplanes < kLevelPlanes && (level >> s.ms_nplanes) != 0) {
-        HIP_TRY(hipMemsetAsync(s.ms_lvl + static_cast<int64_t>(s.ms_nplanes) * ctx->g.n, 0,
-                               ctx->g.n * sizeof(uint64_t), ctx->stream));
+        const uint32_t bit = 1u << s.ms_nplanes;
+        uint64_t* plane = s.ms_lvl + static_cast<int64_t>(s.ms_nplanes) * ctx->g.n;
+        if (!keep_clean) {
+            s.ms_clean &= ~bit;
+            HIP_TRY(hipMemsetAsync(plane, 0, ctx->g.n * sizeof(uint64_t), ctx->stream));
+        } else if (!(s.ms_clean & bit)) {
+            // up to a 4 KB boundary (the rows above n_active are zero already): a length the fill
+            // kernel takes in one dispatch — an odd one cost a second, 5 us, for its tail
+            const int64_t rows = std::min<int64_t>(ctx->g.n, (ctx->g.n_active + 511) & ~int64_t(511));
+            if (rows > 0) HIP_TRY(hipMemsetAsync(plane, 0, rows * sizeof(uint64_t), ctx->stream));
+            s.ms_clean |= bit;
+        }
         ++s.ms_nplanes;
     }
     return TGO_OK;
 }
+// the planes a discovery at `level` writes, as bits of sc.ms_clean (record_level: one per set level bit)
+inline uint32_t ms_planes_written(int32_t level) { return static_cast<uint32_t>(level) & ((1u << kLevelPlanes) - 1u); }
 
 }  // namespace tgo
 

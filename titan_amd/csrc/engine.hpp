@@ -627,9 +627,11 @@ struct Scratch {
     int64_t* ms_rp[2] = {nullptr, nullptr};    // ranged push: list bounds per (entry, range), kMsRangePairs each
     uint64_t* ms_fr = nullptr;      // n: frontier mask
     uint64_t* ms_nx = nullptr;      // n: next-frontier mask
-    uint64_t* ms_lvl = nullptr;     // kLevelPlanes x n: bit r of plane k = bit k of source r's level
+    uint64_t* ms_lvl = nullptr;     // kLevelPlanes x n: bit r of plane k = bit k of source r's level; rows >= n_active
+                                    // are never written (no entries: reached at level 0 only) and stay zero from ms_alloc
     int32_t ms_nplanes = 0;         // planes zeroed (and valid) in the current sweep
     bool ms_masks_zero = false;     // ms_fr and ms_nx are all zero (the last sweep ended on an empty sparse level)
+    uint32_t ms_clean = 0;          // bit k: plane k is zero over [0, n_active) (filled, and no level wrote it since)
     bool ms_srcent_zero = false;    // ms_srcent is zero (published and zeroed by k_publish_turn)
     int64_t* ms_seeds = nullptr;    // 64
     unsigned long long* ms_stat = nullptr;   // 128: reached[64], entries[64]
@@ -825,7 +827,7 @@ hipError_t k_ms_pull(const View& pull, const View& push, int64_t n_active, uint6
                      const uint64_t* fbm, uint64_t* vis, uint64_t* nx, LevelPlanes lvl, Counters* cnt,
                      int32_t next_level, hipStream_t s, int32_t filter_from, uint64_t dense = ~0ULL,
                      const uint64_t* cand = nullptr, MsColdSplit cs = MsColdSplit(), bool count_open = false,
-                     int64_t head = 0);
+                     int64_t head = 0, int32_t compact_chunk = 0);
 // the blocked cold pass and the settle of the rows it completed (msbfs.hip)
 hipError_t k_ms_cold(const int32_t* cadj, const int32_t* crow, int64_t C, const uint64_t* fr, const uint8_t* need,
                      uint64_t* acc, hipStream_t s);
@@ -864,6 +866,9 @@ constexpr double kMsSparseDefault = 1.0 / 16.0;
 // of the lane's own walk.
 constexpr int64_t kMsHeadDefault = 4;
 constexpr int64_t kMsHeadMax = 1 << 20;
+// Default of TGO_MS_CHUNK: the vertices a wave of the compact pull form (ms_pull_compact) scans
+// before it walks the open ones; 512 / 1024 / 2048 (4 bytes of LDS a vertex and wave).
+constexpr int64_t kMsChunkDefault = 1024;
 // Sparse push level (one GPU): nx all zero beforehand; the touched vertices — exactly the next
 // frontier — are appended to qn (length in cnt->qlen, no particular order), and
 // k_ms_settle_sparse settles them over that list (length read on the device): vis, levels,

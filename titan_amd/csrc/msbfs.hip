@@ -13,6 +13,7 @@
 // sources `fresh` of v at level L ORs `fresh` into plane k of v for every set bit k of L —
 // at most log2(L)+1 coalesced 8-byte writes per vertex and level, and planes are zeroed
 // only when the sweep first reaches level 2^k.
+#include <algorithm>
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 #include "frontier.hpp"
@@ -166,6 +167,132 @@ __device__ __forceinline__ void walk_own(const View& pull, int64_t& k0, int64_t 
     }
 }
 
+// One vertex per lane through a pull level: the lane's vertex v (any v >= n_active: no vertex) and
+// its reached mask `seen` (full for no vertex) — offsets, the lane's own walk (short lists, the head
+// of long ones), the whole-wave loop of the long lists left, then the settle of nx / vis / the
+// level planes and the lane's sums.  Called by every lane of the wave together (the long lists'
+// loop is wave-cooperative); ms_pull's words and ms_pull_compact's compacted vertices both go
+// through it.
+template <int kStep, bool kDiag, int kLong, bool kRamp>
+__device__ __forceinline__ void pull_vertex(const View& pull, const View& push, int64_t n_active, uint64_t full,
+        const uint64_t* __restrict__ fr, const uint64_t* __restrict__ fbm, uint64_t* __restrict__ vis,
+        uint64_t* __restrict__ nx, const LevelPlanes& lvl, int32_t next_level, int32_t filter_from, uint64_t dense,
+        const uint64_t* __restrict__ cand, const MsColdSplit& cs, int64_t coop, bool count_open, int64_t head,
+        int64_t v, uint64_t seen, unsigned long long& nv, unsigned long long& mf, unsigned long long& bits,
+        unsigned long long& mu, unsigned long long* dg) {
+    const int32_t hot_lim = cs.hot_lim;
+    const uint64_t open = full & ~seen;
+    // the walk only has to cover the dense sources; the sparse ones come from the push
+    // candidates (cand, exact over every entry of their frontiers)
+    const uint64_t want = open & dense;
+    int64_t b0 = 0, e0 = 0, b1 = 0, e1 = 0;
+    if (open) {
+        b0 = pull.off0[v]; e0 = pull.off0[v + 1];
+        if (pull.nlists > 1) { b1 = pull.off1[v]; e1 = pull.off1[v + 1]; }
+    }
+    const int64_t deg = (e0 - b0) + (e1 - b1);
+    const bool is_big = want != 0 && deg > coop;
+    uint64_t acc = 0;
+    bool cut = false;                                     // a list went on past hot_lim
+    int64_t h0 = b0, h1 = b1;                             // where the lane's own walk stands
+    // short lists to their end and the heads of the long ones in the same trips
+    if (want)
+        walk_own<kStep, kDiag>(pull, h0, e0, h1, e1, is_big ? head : INT64_MAX, want, fr, fbm, filter_from, hot_lim,
+                               acc, cut, dg, is_big ? 5 : 0, is_big ? 8 : 1);
+    const bool head_done = is_big && (acc & want) == want;   // covered within the head
+    if (kDiag) {
+        if (want && !is_big) { ++dg[3]; if ((acc & want) == want) ++dg[4]; }
+        if (head_done) { ++dg[6]; ++dg[7]; ++dg[diag_cover_bucket((h0 - b0) + (h1 - b1))]; }
+    }
+    unsigned long long big = __ballot(is_big && !head_done);
+    while (big) {
+        const int src = __ffsll(static_cast<long long>(big)) - 1;
+        big &= big - 1;
+        const uint64_t wsrc = __shfl(want, src, 64);
+        uint64_t a = __shfl(acc, src, 64);                // what the head found
+        bool wcut = false;                                // wave-uniform
+        int64_t pos = kDiag ? __shfl((h0 - b0) + (h1 - b1), src, 64) : 0;   // entries before this trip
+        int64_t cover = -1;                               // diagnostics: the entry that covered the walk
+        for (int l = 0; l < 2; ++l) {
+            const int64_t bb = __shfl(l == 0 ? h0 : h1, src, 64);
+            const int64_t ee = __shfl(l == 0 ? e0 : e1, src, 64);
+            const int32_t* adj = l == 0 ? pull.adj0 : pull.adj1;
+            bool done = false;
+            bool first = kRamp && l == 0;
+            for (int64_t k = bb; k < ee && !done;) {
+                const int jl = first ? 1 : kLong;                 // wave-uniform
+                int32_t u[kLong];
+                bool hc = false;
+#pragma unroll
+                for (int j = 0; j < kLong; ++j) {
+                    const int64_t x = k + j * 64 + lane();
+                    u[j] = (j < jl && x < ee) ? __builtin_nontemporal_load(adj + x) : -1;
+                    if (u[j] >= hot_lim) { u[j] = -1; hc = true; }
+                }
+                const int64_t trip = min(static_cast<int64_t>(jl) * 64, ee - k);
+                k += static_cast<int64_t>(jl) * 64;
+                first = false;
+                if (__ballot(hc)) { done = true; wcut = true; }   // the rest of the list is cold
+                bool f[kLong];
+#pragma unroll
+                for (int j = 0; j < kLong; ++j) f[j] = u[j] >= 0 && maybe_frontier(fbm, u[j], filter_from);
+                uint64_t m = 0;
+#pragma unroll
+                for (int j = 0; j < kLong; ++j)
+                    if (f[j]) m |= fr[u[j]];
+                if (kDiag && cover < 0) {
+                    // the first lane at which the masks up to it cover the walk
+                    uint64_t p = m;
+                    for (int o = 1; o < 64; o <<= 1) {
+                        const uint64_t y = __shfl_up(p, o, 64);
+                        if (lane() >= o) p |= y;
+                    }
+                    const unsigned long long cv = __ballot(((a | p) & wsrc) == wsrc);
+                    if (cv) cover = pos + (kLong == 1 ? __ffsll(static_cast<long long>(cv)) : trip);
+                    pos += trip;
+                }
+                for (int off = 32; off > 0; off >>= 1) m |= __shfl_xor(m, off, 64);
+                if (kDiag)
+                    for (int j = 0; j < kLong; ++j)
+                        if (u[j] >= 0) ++dg[u[j] < kDiagHot ? 8 : 9];
+                a |= m;
+                done = done || (a & wsrc) == wsrc;
+                if (kDiag && lane() == src)
+                    for (int j = 0; j < kLong; ++j) dg[5] += u[j] >= 0 ? 1 : 0;
+            }
+            if ((a & wsrc) == wsrc) break;
+        }
+        if (lane() == src) {
+            acc = a;
+            cut = wcut;
+            if (kDiag) {
+                ++dg[6];
+                if ((a & wsrc) == wsrc) ++dg[7];
+                ++dg[(a & wsrc) == wsrc && cover >= 0 ? diag_cover_bucket(cover) : 16];
+            }
+        }
+    }
+    if (cut && (acc & want) != want && v < n_active) {   // left to the cold pass
+        cs.acc[v] = acc;
+        cs.need[v] = 1;
+        return;
+    }
+    if (cand && open && v < n_active) acc |= cand[v];
+    const uint64_t fresh = acc & open;
+    if (v < n_active) {
+        nx[v] = fresh;
+        if (fresh) vis[v] = seen | fresh;
+    }
+    if (fresh) {
+        record_level(v, fresh, next_level, lvl);
+        ++nv;
+        mf += static_cast<unsigned long long>(push_degree(push, v));
+        bits += static_cast<unsigned long long>(__popcll(fresh));
+    }
+    // still open after this level: its list is what a pull of the next level walks
+    if (count_open && (open & ~fresh)) mu += static_cast<unsigned long long>(deg);
+}
+
 // kStep: entries per dependent round trip of a lane's own list; kLong: entries per lane per
 // trip of a wave-cooperative long list (kLong * 64 per trip)
 // cs (MsColdSplit, hot_lim < INT32_MAX): the walk reads only neighbours < hot_lim (lists are
@@ -180,12 +307,15 @@ __device__ __forceinline__ void walk_own(const View& pull, int64_t& k0, int64_t 
 // whole wave, one list after another, from the position the head reached.  0 = off.
 // count_open: also sum the list entries of the vertices still open after the level (cnt->open; the
 // rows a cold split leaves to ms_finish are not in it).
+// This is the word form: a wave per word of 64 consecutive vertices, whatever the word holds.  The
+// levels past the frontier's peak, where most words hold few open vertices or none, run
+// ms_pull_compact below (same per-vertex body, pull_vertex); the cold split, the source split's
+// candidates, the diagnostic tallies and the partitioned sweep stay here.
 template <int kStep, bool kDiag = false, int kLong = 4, bool kRamp = false>
 __global__ void __launch_bounds__(kBlock) ms_pull(View pull, View push, int64_t n_active, uint64_t full,
         const uint64_t* __restrict__ fr, const uint64_t* __restrict__ fbm, uint64_t* __restrict__ vis,
         uint64_t* __restrict__ nx, LevelPlanes lvl, Counters* cnt, int32_t next_level, int32_t filter_from,
         uint64_t dense, const uint64_t* __restrict__ cand, MsColdSplit cs, int64_t coop, bool count_open, int64_t head) {
-    const int32_t hot_lim = cs.hot_lim;
     unsigned long long nv = 0, mf = 0, bits = 0, mu = 0;
     unsigned long long dg[kDiagWords] = {};
     const int64_t words = (n_active + 63) >> 6;
@@ -196,116 +326,8 @@ __global__ void __launch_bounds__(kBlock) ms_pull(View pull, View push, int64_t 
         const int64_t wd = b + (threadIdx.x >> 6);
         const int64_t v = (wd << 6) + lane();
         const uint64_t seen = v < n_active ? vis[v] : full;
-        const uint64_t open = full & ~seen;
-        // the walk only has to cover the dense sources; the sparse ones come from the push
-        // candidates (cand, exact over every entry of their frontiers)
-        const uint64_t want = open & dense;
-        int64_t b0 = 0, e0 = 0, b1 = 0, e1 = 0;
-        if (open) {
-            b0 = pull.off0[v]; e0 = pull.off0[v + 1];
-            if (pull.nlists > 1) { b1 = pull.off1[v]; e1 = pull.off1[v + 1]; }
-        }
-        const int64_t deg = (e0 - b0) + (e1 - b1);
-        const bool is_big = want != 0 && deg > coop;
-        uint64_t acc = 0;
-        bool cut = false;                                     // a list went on past hot_lim
-        int64_t h0 = b0, h1 = b1;                             // where the lane's own walk stands
-        // short lists to their end and the heads of the long ones in the same trips
-        if (want)
-            walk_own<kStep, kDiag>(pull, h0, e0, h1, e1, is_big ? head : INT64_MAX, want, fr, fbm, filter_from, hot_lim,
-                                   acc, cut, dg, is_big ? 5 : 0, is_big ? 8 : 1);
-        const bool head_done = is_big && (acc & want) == want;   // covered within the head
-        if (kDiag) {
-            if (want && !is_big) { ++dg[3]; if ((acc & want) == want) ++dg[4]; }
-            if (head_done) { ++dg[6]; ++dg[7]; ++dg[diag_cover_bucket((h0 - b0) + (h1 - b1))]; }
-        }
-        unsigned long long big = __ballot(is_big && !head_done);
-        while (big) {
-            const int src = __ffsll(static_cast<long long>(big)) - 1;
-            big &= big - 1;
-            const uint64_t wsrc = __shfl(want, src, 64);
-            uint64_t a = __shfl(acc, src, 64);                // what the head found
-            bool wcut = false;                                // wave-uniform
-            int64_t pos = kDiag ? __shfl((h0 - b0) + (h1 - b1), src, 64) : 0;   // entries before this trip
-            int64_t cover = -1;                               // diagnostics: the entry that covered the walk
-            for (int l = 0; l < 2; ++l) {
-                const int64_t bb = __shfl(l == 0 ? h0 : h1, src, 64);
-                const int64_t ee = __shfl(l == 0 ? e0 : e1, src, 64);
-                const int32_t* adj = l == 0 ? pull.adj0 : pull.adj1;
-                bool done = false;
-                bool first = kRamp && l == 0;
-                for (int64_t k = bb; k < ee && !done;) {
-                    const int jl = first ? 1 : kLong;                 // wave-uniform
-                    int32_t u[kLong];
-                    bool hc = false;
-#pragma unroll
-                    for (int j = 0; j < kLong; ++j) {
-                        const int64_t x = k + j * 64 + lane();
-                        u[j] = (j < jl && x < ee) ? __builtin_nontemporal_load(adj + x) : -1;
-                        if (u[j] >= hot_lim) { u[j] = -1; hc = true; }
-                    }
-                    const int64_t trip = min(static_cast<int64_t>(jl) * 64, ee - k);
-                    k += static_cast<int64_t>(jl) * 64;
-                    first = false;
-                    if (__ballot(hc)) { done = true; wcut = true; }   // the rest of the list is cold
-                    bool f[kLong];
-#pragma unroll
-                    for (int j = 0; j < kLong; ++j) f[j] = u[j] >= 0 && maybe_frontier(fbm, u[j], filter_from);
-                    uint64_t m = 0;
-#pragma unroll
-                    for (int j = 0; j < kLong; ++j)
-                        if (f[j]) m |= fr[u[j]];
-                    if (kDiag && cover < 0) {
-                        // the first lane at which the masks up to it cover the walk
-                        uint64_t p = m;
-                        for (int o = 1; o < 64; o <<= 1) {
-                            const uint64_t y = __shfl_up(p, o, 64);
-                            if (lane() >= o) p |= y;
-                        }
-                        const unsigned long long cv = __ballot(((a | p) & wsrc) == wsrc);
-                        if (cv) cover = pos + (kLong == 1 ? __ffsll(static_cast<long long>(cv)) : trip);
-                        pos += trip;
-                    }
-                    for (int off = 32; off > 0; off >>= 1) m |= __shfl_xor(m, off, 64);
-                    if (kDiag)
-                        for (int j = 0; j < kLong; ++j)
-                            if (u[j] >= 0) ++dg[u[j] < kDiagHot ? 8 : 9];
-                    a |= m;
-                    done = done || (a & wsrc) == wsrc;
-                    if (kDiag && lane() == src)
-                        for (int j = 0; j < kLong; ++j) dg[5] += u[j] >= 0 ? 1 : 0;
-                }
-                if ((a & wsrc) == wsrc) break;
-            }
-            if (lane() == src) {
-                acc = a;
-                cut = wcut;
-                if (kDiag) {
-                    ++dg[6];
-                    if ((a & wsrc) == wsrc) ++dg[7];
-                    ++dg[(a & wsrc) == wsrc && cover >= 0 ? diag_cover_bucket(cover) : 16];
-                }
-            }
-        }
-        if (cut && (acc & want) != want && v < n_active) {   // left to the cold pass
-            cs.acc[v] = acc;
-            cs.need[v] = 1;
-            continue;
-        }
-        if (cand && open && v < n_active) acc |= cand[v];
-        const uint64_t fresh = acc & open;
-        if (v < n_active) {
-            nx[v] = fresh;
-            if (fresh) vis[v] = seen | fresh;
-        }
-        if (fresh) {
-            record_level(v, fresh, next_level, lvl);
-            ++nv;
-            mf += static_cast<unsigned long long>(push_degree(push, v));
-            bits += static_cast<unsigned long long>(__popcll(fresh));
-        }
-        // still open after this level: its list is what a pull of the next level walks
-        if (count_open && (open & ~fresh)) mu += static_cast<unsigned long long>(deg);
+        pull_vertex<kStep, kDiag, kLong, kRamp>(pull, push, n_active, full, fr, fbm, vis, nx, lvl, next_level, filter_from,
+                                                dense, cand, cs, coop, count_open, head, v, seen, nv, mf, bits, mu, dg);
     }
     if (kDiag) {
         for (int i = 0; i < kDiagWords; ++i) {
@@ -313,6 +335,84 @@ __global__ void __launch_bounds__(kBlock) ms_pull(View pull, View push, int64_t 
             for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
             if (lane() == 0 && x) atomicAdd(&g_ms_diag[i], x);
         }
+    }
+    count_flush(cnt, nv, mf, bits, mu);
+}
+
+// The compact form of a pull level, for the levels after the frontier's peak where few vertices
+// are still open (RMAT-24: 20 % at the first such level, 0.15 % and less after it) and a word of
+// 64 vertices keeps a handful of ms_pull's lanes busy, or none.  A wave takes a chunk of `chunk`
+// vertices (a multiple of 64 * kCompactScan) — chunk / 64 words a grid stride apart, as ms_pull's
+// loop would visit them: the rows are in degree order, and a chunk of consecutive words gave one
+// wave a thousand hubs when every vertex is open — in two phases:
+//   scan: the reached masks of kCompactScan words at a time, loaded together at a clamped index
+//         (a load under a per-lane condition is serialised) and masked after;
+//         a closed vertex gets its nx = 0 right here (coalesced), the ids of the open ones are
+//         compacted by ballot + popcount into the wave's slice of LDS (4 bytes a vertex);
+//   walk: the compacted ids 64 at a time, one per lane and every lane busy, through pull_vertex —
+//         the body ms_pull's words go through (the reached mask is read again: an L2 hit).
+// No block barrier and no state between kernels: the waves of a block stay independent, the grid
+// is about one chunk per wave, and the block ends in one count_flush like ms_pull's.  Every
+// source is pulled (no candidates, no cold split: those levels run the word form).
+constexpr int kCompactScan = 8;
+template <int kStep, int kLong>
+__global__ void __launch_bounds__(kBlock) ms_pull_compact(View pull, View push, int64_t n_active, uint64_t full,
+        const uint64_t* __restrict__ fr, const uint64_t* __restrict__ fbm, uint64_t* __restrict__ vis,
+        uint64_t* __restrict__ nx, LevelPlanes lvl, Counters* cnt, int32_t next_level, int32_t filter_from,
+        int64_t coop, bool count_open, int64_t head, int32_t chunk) {
+    extern __shared__ int32_t s_open[];                       // kWavesPerBlock slices of `chunk` ids
+    unsigned long long nv = 0, mf = 0, bits = 0, mu = 0;
+    const MsColdSplit cs;
+    const int64_t words = (n_active + 63) >> 6;
+    const int32_t per = chunk >> 6;                           // words a chunk
+    const int64_t chunks = (words + per - 1) / per;
+    const int64_t last = n_active > 0 ? n_active - 1 : 0;     // the masks hold n + 1 words: row 0 exists
+    const unsigned long long below = (1ULL << lane()) - 1ULL;
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));   // scalar for the compiler too
+    int32_t* ids = s_open + wave * chunk;
+    for (int64_t c = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave; c < chunks;
+         c += static_cast<int64_t>(gridDim.x) * kWavesPerBlock) {
+        int32_t nopen = 0;                                    // wave-uniform
+        for (int32_t w = 0; w < per; w += kCompactScan) {
+            // word j of chunk c is word c + j * chunks: rows are in degree order, so consecutive
+            // words would hand all the hubs to the first few waves
+            // (the word index is wave-uniform: one scalar base per load, the lane's offset clamped to
+            // the last row — only the last word can be short)
+            uint64_t sv[kCompactScan];
+#pragma unroll
+            for (int j = 0; j < kCompactScan; ++j) {
+                const int64_t wd = min(c + (w + j) * chunks, words - 1);
+                const int32_t lim = static_cast<int32_t>(min(last - (wd << 6), static_cast<int64_t>(63)));
+                sv[j] = (vis + (wd << 6))[min(lane(), lim)];
+            }
+#pragma unroll
+            for (int j = 0; j < kCompactScan; ++j) {
+                const int64_t wd = c + (w + j) * chunks;
+                const int64_t v = (wd << 6) + lane();
+                const bool live = wd < words && v < n_active;
+                const bool is_open = live && (full & ~sv[j]) != 0;
+                if (live && !is_open) nx[v] = 0;
+                const unsigned long long m = __ballot(is_open);
+                if (is_open) ids[nopen + __popcll(m & below)] = static_cast<int32_t>(v);
+                nopen += __popcll(m);
+            }
+        }
+        // the ids were written by other lanes of this wave: LDS operations of a wave complete in
+        // order, the fence keeps the compiler from moving the reads above the writes
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (int32_t i = 0; i < nopen; i += 64) {
+            const bool has = i + lane() < nopen;
+            const int64_t v = has ? ids[i + lane()] : n_active;
+            const uint64_t got = vis[min(v, last)];
+            const uint64_t seen = has ? got : full;
+            pull_vertex<kStep, false, kLong, false>(pull, push, n_active, full, fr, fbm, vis, nx, lvl, next_level,
+                                                    filter_from, full, nullptr, cs, coop, count_open, head, v, seen, nv, mf,
+                                                    bits, mu, nullptr);
+        }
+        // the next chunk's ids overwrite these: every lane has read its own by now
+        __builtin_amdgcn_wave_barrier();
     }
     count_flush(cnt, nv, mf, bits, mu);
 }
@@ -1095,7 +1195,20 @@ hipError_t k_ms_seed(const int64_t* seeds, int nseeds, uint64_t* vis, uint64_t* 
 hipError_t k_ms_pull(const View& pull, const View& push, int64_t n_active, uint64_t full, const uint64_t* fr,
                      const uint64_t* fbm, uint64_t* vis, uint64_t* nx, LevelPlanes lvl, Counters* cnt,
                      int32_t next_level, hipStream_t s, int32_t filter_from, uint64_t dense, const uint64_t* cand,
-                     MsColdSplit cs, bool count_open, int64_t head) {
+                     MsColdSplit cs, bool count_open, int64_t head, int32_t compact_chunk) {
+    static const int64_t coop_env = env_i64("TGO_MS_COOP", kCoop);
+    if (compact_chunk > 0) {
+        // the compact form (the product's trips: 4 entries a lane, 64-entry long trips): about one
+        // chunk per wave — its block ends in count_flush's atomics like the word form's, on a
+        // quarter or less of its blocks
+        if (dense != full || cand || cs.acc || compact_chunk % (64 * kCompactScan) != 0) return hipErrorInvalidValue;
+        const int64_t chunks = ((n_active + 63) / 64 + compact_chunk / 64 - 1) / (compact_chunk / 64);
+        const int64_t blocks = std::min<int64_t>(std::max<int64_t>((chunks + kWavesPerBlock - 1) / kWavesPerBlock, 1), 8192);
+        const size_t lds = static_cast<size_t>(kWavesPerBlock) * compact_chunk * sizeof(int32_t);
+        ms_pull_compact<4, 1><<<static_cast<int>(blocks), kBlock, lds, s>>>(pull, push, n_active, full, fr, fbm, vis, nx,
+                lvl, cnt, next_level, filter_from, coop_env, count_open, head, compact_chunk);
+        return hipGetLastError();
+    }
     // TGO_MS_STEP: entries a lane loads per round trip of its own list (4 default since the
     // trips are branch-free, round 6: sweep 3.623 -> 3.562 ms against 8 with the branchy trips,
     // profiles/r06ms1_ms_branchfree_ab.log; 8 / 16 probes)
@@ -1108,7 +1221,7 @@ hipError_t k_ms_pull(const View& pull, const View& push, int64_t n_active, uint6
     // TGO_MS_RAMP=1 (with TGO_MS_LONG=4): a long list's first trip reads 64 entries
     static const bool ramp = env_i64("TGO_MS_RAMP", 0) != 0;
     // TGO_MS_COOP: lists longer than this are walked by the whole wave (64 default)
-    static const int64_t coop = env_i64("TGO_MS_COOP", kCoop);
+    const int64_t coop = coop_env;
     const dim3 grid(grid_for(n_active, 8192));
 #define TGO_MS_PULL(S, D, LG, R) ms_pull<S, D, LG, R><<<grid, kBlock, 0, s>>>(pull, push, n_active, full, fr, fbm, vis, \
         nx, lvl, cnt, next_level, filter_from, dense, cand, cs, coop, count_open, head)

@@ -24,12 +24,12 @@ struct Event {
     double ts = 0, dur = 0;            // microseconds since the trace base
     uint64_t tid = 0;
     int dev = 0;                       // 0 host span, 1 device span
-    TraceArg a{nullptr, 0}, b{nullptr, 0};
+    TraceArg a{nullptr, 0}, b{nullptr, 0}, c{nullptr, 0};
 };
 struct Pending {
     hipStream_t s;
     std::string name;
-    TraceArg a, b;
+    TraceArg a, b, c;
     hipEvent_t e0, e1;
 };
 
@@ -83,7 +83,7 @@ int write_json(const char* path) {
                      e.dev ? "device" : "host", e.ts, e.dur, e.dev ? 1 : 0, static_cast<unsigned long long>(e.tid));
         std::fprintf(f, ", \"args\": {");
         bool first = true;
-        for (const TraceArg& a : {e.a, e.b}) {
+        for (const TraceArg& a : {e.a, e.b, e.c}) {
             if (!a.key) continue;
             std::fprintf(f, "%s\"%s\": %lld", first ? "" : ", ", a.key, static_cast<long long>(a.value));
             first = false;
@@ -135,7 +135,8 @@ Span::~Span() {
     S.events.push_back(std::move(e));
 }
 
-DevSpan::DevSpan(hipStream_t s, const char* name, TraceArg a, TraceArg b) : s_(s), name_(name), a_(a), b_(b) {
+DevSpan::DevSpan(hipStream_t s, const char* name, TraceArg a, TraceArg b, TraceArg c)
+    : s_(s), name_(name), a_(a), b_(b), c_(c) {
     const int f = g_trace_flags.load(std::memory_order_relaxed);
     if (!f) return;
     if (f & kTraceRoctx) { roctxRangePushA(name); roctx_ = true; }
@@ -152,7 +153,7 @@ void DevSpan::end() {
     if (hipEventRecord(e1_, s_) != hipSuccess) return;
     State& S = st();
     std::lock_guard<std::mutex> lk(S.mu);
-    S.pending.push_back({s_, name_, a_, b_, e0_, e1_});
+    S.pending.push_back({s_, name_, a_, b_, c_, e0_, e1_});
 }
 
 void trace_complete(const std::string& name, double dur_us) {
@@ -196,6 +197,7 @@ void trace_resolve(hipStream_t s) {
         e.dev = 1;
         e.a = p.a;
         e.b = p.b;
+        e.c = p.c;
         out.push_back(std::move(e));
     }
     std::lock_guard<std::mutex> lk(S.mu);

@@ -47,15 +47,17 @@ private:
 // A device span on stream s: events recorded now and at end(); resolved by trace_resolve.
 class DevSpan {
 public:
-    DevSpan(hipStream_t s, const char* name, TraceArg a = {nullptr, 0}, TraceArg b = {nullptr, 0});
+    DevSpan(hipStream_t s, const char* name, TraceArg a = {nullptr, 0}, TraceArg b = {nullptr, 0},
+            TraceArg c = {nullptr, 0});
     ~DevSpan() { end(); }
     void end();
+    void set_third(int64_t value) { c_.value = value; }   // an argument only known inside the span
     DevSpan(const DevSpan&) = delete;
     DevSpan& operator=(const DevSpan&) = delete;
 private:
     hipStream_t s_;
     const char* name_;
-    TraceArg a_, b_;
+    TraceArg a_, b_, c_;
     hipEvent_t e0_ = nullptr, e1_ = nullptr;
     bool roctx_ = false, open_ = false;
 };
