@@ -492,6 +492,59 @@ typedef struct { int64_t degeneracy, innermost, simple_edges; int32_t levels, ro
 int  tgo_kcore(tgo_ctx* ctx, const tgo_core_args* args, int64_t* core_out, tgo_core_info* info);
 int  tgo_copy_cores(tgo_ctx* ctx, int64_t* core_out);
 
+/* ---- k-truss decomposition -------------------------------------------------------------
+ * Over the same simple undirected projection as tgo_triangles / tgo_kcore (u ~ v iff u != v and an
+ * OUT or IN entry of u names v; parallel edges, the two directions of a pair and self-loops
+ * collapse; a vertex cut counts as its canonical vertex).  Per simple edge e = {u, v}:
+ *   support[e]  |N(u) ∩ N(v)|, the triangles through e
+ *   truss[e]    the largest k such that e lies in a subgraph of the projection in which every edge
+ *               is in at least k - 2 triangles of that subgraph; 2 for an edge in no triangle
+ * and per vertex in row order:
+ *   vtruss[v]   the largest truss[e] over the simple edges at v; 0 for a vertex without a neighbour
+ * The decomposition is unique and all values are integers: results are bit-identical run to run
+ * and for every value of the path thresholds below.  args:
+ *   k              0: the full decomposition.  k >= 2: only the levels below k are peeled; every
+ *                  reported edge value is min(truss[e], k), and vtruss and info are computed from
+ *                  these clamped values — truss >= k marks the k-truss, and the levels above are
+ *                  never walked.  k = 1 and k < 0: TGO_E_INVALID
+ *   wave_row, block_row, peel_wave_row
+ *                  path thresholds: 0 = the default, a value >= 1 = the threshold, a negative one:
+ *                  TGO_E_INVALID.  wave_row / block_row: forward-row lengths of the support pass,
+ *                  with the meaning of TGO_TUNE_TRI_WAVE_ROW / _BLOCK_ROW.  peel_wave_row: a
+ *                  frontier edge whose shorter endpoint row has at least this many entries is
+ *                  intersected by a whole wave instead of one lane
+ * info:
+ *   max_truss        the largest reported value
+ *   innermost_edges  the edges at max_truss
+ *   triangles        sum(support) / 3 (= tgo_tri_info.triangles)
+ *   simple_edges     the simple edges
+ *   levels           distinct reported values; deterministic; also tgo_stats.iterations
+ *   rounds           peel launches of this run (the edges in no triangle are settled without one).
+ *                    A DIAGNOSTIC: it may differ between runs and between threshold values
+ * A projection without any edge is not peeled: every vtruss is 0 and info is all zero.
+ * tgo_copy_truss_edges fills info->simple_edges entries of each array given (each may be NULL):
+ * every simple edge exactly once, as Titan ids (canonical for a vertex cut) with u_ids[i] < v_ids[i],
+ * its reported truss value and its support (the triangles through it, not the peeled working
+ * value).  The order is unspecified, but the same from run to run on one load.
+ * args->scope must be TGO_SCOPE_BOTH_E and the loaded scope (else TGO_E_INVALID), args->flags 0.
+ * Lists that are not each other's transpose (tgo_load_csr with asymmetric rows): TGO_E_UNSUPPORTED;
+ * so does a partitioned ctx, and so do more than 2^31 - 2 simple edges (edge ids are int32).  A
+ * failed call leaves the ctx usable.  vtruss_out NULL: the result stays on the device
+ * (tgo_copy_truss; tgo_result_rows kind TGO_RESULT_TRUSS).  Both copy calls after another program:
+ * TGO_E_STATE.  The forward lists are shared with tgo_triangles, the sorted simple adjacency
+ * (8 bytes per simple edge + 8 (n + 1)) with tgo_betweenness, the Titan ids by internal index (8 n)
+ * with tgo_components; the edge ids of the adjacency entries (8 bytes per simple edge) and the
+ * per-edge arrays (32 bytes per simple edge: row, support, working support, value, two queues and
+ * two alive lists) are built on the first run of a load and stay cached with it
+ * (tgo_stats.device_bytes). */
+typedef struct { int32_t scope; int32_t flags; int32_t k;
+                 int32_t wave_row; int32_t block_row; int32_t peel_wave_row; } tgo_truss_args;
+typedef struct { int64_t max_truss, innermost_edges, triangles, simple_edges;
+                 int32_t levels, rounds; } tgo_truss_info;
+int  tgo_ktruss(tgo_ctx* ctx, const tgo_truss_args* args, int64_t* vtruss_out, tgo_truss_info* info);
+int  tgo_copy_truss(tgo_ctx* ctx, int64_t* vtruss_out);
+int  tgo_copy_truss_edges(tgo_ctx* ctx, int64_t* u_ids, int64_t* v_ids, int64_t* truss, int64_t* support);
+
 /* ---- Strongly connected components -----------------------------------------------------
  * Over the directed graph of a bothE load: an arc u -> v iff an OUT entry of u names v, which is
  * to say an IN entry of v names u.  Parallel arcs change nothing; neither does a self-loop (a vertex
@@ -768,6 +821,7 @@ int  tgo_dense_ids(tgo_ctx* ctx, const int64_t* titan_ids, int64_t count, int64_
  *   CLOSENESS tgo_closeness's closeness (key_ids[0]) and harmonic centrality (key_ids[1]), two Doubles on
  *             every executed vertex, encoded exactly as PAGERANK's pair; any other typed key:
  *             TGO_E_INVALID
+ *   TRUSS     tgo_ktruss's vtruss (the largest truss value at the vertex), encoded exactly as CORE
  * Compute keys are typed property keys of those datatypes, or generic keys (TGO_DT_OBJECT: what
  * getOrCreatePropertyKey makes for a key the program sets without a schema, DefaultSchemaMaker
  * .java:46-48), whose values carry their class (Long 13, Double 20, Integer 12).  Relation ids are
@@ -778,11 +832,11 @@ int  tgo_dense_ids(tgo_ctx* ctx, const int64_t* titan_ids, int64_t count, int64_
 typedef enum { TGO_RESULT_DISTANCE = 0, TGO_RESULT_PAGERANK = 1, TGO_RESULT_DEGREE = 2,
                TGO_RESULT_VALUES = 3, TGO_RESULT_COMPONENT = 4, TGO_RESULT_TRIANGLES = 5,
                TGO_RESULT_CORE = 6, TGO_RESULT_SCC = 7, TGO_RESULT_BETWEENNESS = 8,
-               TGO_RESULT_PEER_PRESSURE = 9, TGO_RESULT_CLOSENESS = 10 } tgo_result_kind;
+               TGO_RESULT_PEER_PRESSURE = 9, TGO_RESULT_CLOSENESS = 10, TGO_RESULT_TRUSS = 11 } tgo_result_kind;
 typedef struct {
     int32_t kind;                 /* tgo_result_kind                                          */
     int32_t reserved;             /* TGO_RESULT_VALUES: tgo_value_type of the values           */
-    int64_t key_ids[2];           /* [0] DISTANCE / PAGE_RANK / DEGREE / COMPONENT / TRIANGLES / CORE / SCC / BETWEENNESS / PEER_PRESSURE / CLOSENESS key; [1] OUTGOING_EDGE_COUNT / CLUSTERING / HARMONIC */
+    int64_t key_ids[2];           /* [0] DISTANCE / PAGE_RANK / DEGREE / COMPONENT / TRIANGLES / CORE / SCC / BETWEENNESS / PEER_PRESSURE / CLOSENESS / TRUSS key; [1] OUTGOING_EDGE_COUNT / CLUSTERING / HARMONIC */
     int32_t datatypes[2];         /* tgo_datatype of each key                                  */
     int64_t relation_id_base;
 } tgo_result_args;

@@ -316,6 +316,23 @@ JNIEXPORT jlongArray JNICALL JFN(kcore)(JNIEnv* env, jclass cls, jlong h) {
     return distances(env, h, run_kcore, &a);
 }
 
+/* tgo_ktruss over the bothE load: every vertex's truss number (the largest truss value of an edge at
+ * it, clamped at k when k >= 2; k = 0: the full decomposition) in row order, or NULL on error (the
+ * levels are tgo_stats.iterations afterwards; write-back: tgo_result_rows kind TGO_RESULT_TRUSS).
+ * The per-edge list stays a C call (tgo_copy_truss_edges). */
+static int run_ktruss(tgo_ctx* c, const void* a, int64_t* o) {
+    return tgo_ktruss(c, (const tgo_truss_args*)a, o, NULL);
+}
+
+JNIEXPORT jlongArray JNICALL JFN(ktruss)(JNIEnv* env, jclass cls, jlong h, jint k) {
+    (void)cls;
+    tgo_truss_args a;
+    memset(&a, 0, sizeof a);
+    a.scope = TGO_SCOPE_BOTH_E;
+    a.k = (int32_t)k;
+    return distances(env, h, run_ktruss, &a);
+}
+
 /* tgo_scc over the bothE load read as a directed graph: every vertex's component label (the smallest
  * Titan id of its strongly connected component) in row order, or NULL on error (the device launches
  * are tgo_stats.iterations afterwards; write-back: tgo_result_rows kind TGO_RESULT_SCC). */

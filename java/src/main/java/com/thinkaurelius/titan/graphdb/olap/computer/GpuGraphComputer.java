@@ -47,6 +47,7 @@ import java.util.concurrent.Future;
  * (weakly connected components over bothE, tgo_components), a TriangleCountVertexProgram
  * (triangles and clustering coefficients of the simple undirected projection, tgo_triangles) and
  * a KCoreVertexProgram (core numbers of the same projection, tgo_kcore),
+ * a KTrussVertexProgram (truss numbers of the same projection, tgo_ktruss),
  * a StronglyConnectedComponentsVertexProgram (bothE read as a directed graph, tgo_scc),
  * a BetweennessCentralityVertexProgram (Brandes' betweenness over either reading, tgo_betweenness),
  * TinkerPop's PeerPressureVertexProgram (one vote per edge, exact integer tallies, tgo_peer_pressure),
@@ -547,6 +548,8 @@ public class GpuGraphComputer implements TitanGraphComputer {
                     return new TriangleCount();
                 case "com.thinkaurelius.titan.olap.KCoreVertexProgram":
                     return new KCore();
+                case "com.thinkaurelius.titan.olap.KTrussVertexProgram":
+                    return new KTruss(conf.getInt("titan.kTruss.k", 0));
                 case "com.thinkaurelius.titan.olap.StronglyConnectedComponentsVertexProgram":
                     return new StronglyConnectedComponents();
                 case "com.thinkaurelius.titan.olap.BetweennessCentralityVertexProgram":
@@ -795,6 +798,35 @@ public class GpuGraphComputer implements TitanGraphComputer {
         void emit(long[] ids, Map<String, Object> values, FulgoraMapEmitter emitter) {
             long[] c = (long[]) values.get(CORE);
             for (int i = 0; i < ids.length; i++) emitter.emit(ids[i], c[i]);
+        }
+    }
+
+    /**
+     * k-truss decomposition over bothE on the simple undirected projection (tgo_ktruss): TRUSS = the
+     * largest truss value of an edge at the vertex, an edge's value being the largest k such that it
+     * lies in a subgraph whose edges are all in at least k - 2 triangles of it.  k (titan.kTruss.k;
+     * 0: every level) clamps the values and stops the peel below that level.  The iteration reported
+     * is the number of distinct edge values (the peel's levels), known after run().
+     */
+    static final class KTruss extends DeviceProgram {
+        static final String TRUSS = "titan.kTruss.trussNumber";
+        final int k;
+        private int levels;
+        KTruss(int k) { this.k = k; }
+        int scope() { return TgoNative.SCOPE_BOTH_E; }
+        int iterations() { return levels; }
+        int resultKind() { return TgoNative.RESULT_TRUSS; }
+        String[] computeKeys() { return new String[]{TRUSS}; }
+        int[] computeKeyTypes() { return new int[]{TgoNative.DT_LONG}; }
+        Map<String, Object> run(long ctx) {
+            Map<String, Object> v = new HashMap<>();
+            v.put(TRUSS, TgoNative.checked(ctx, TgoNative.ktruss(ctx, k)));
+            levels = (int) TgoNative.stats(ctx)[3];
+            return v;
+        }
+        void emit(long[] ids, Map<String, Object> values, FulgoraMapEmitter emitter) {
+            long[] t = (long[]) values.get(TRUSS);
+            for (int i = 0; i < ids.length; i++) emitter.emit(ids[i], t[i]);
         }
     }
 

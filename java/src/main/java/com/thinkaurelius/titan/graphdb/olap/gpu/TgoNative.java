@@ -96,6 +96,15 @@ public final class TgoNative {
     public static native long[] kcore(long ctx);
 
     /**
+     * tgo_ktruss over a bothE load: every vertex's truss number on the simple undirected projection
+     * (the largest truss value of an edge at it; 0 without a neighbour), in row order; null on
+     * failure.  k = 0: the full decomposition; k >= 2: only the levels below k are peeled and the
+     * values are clamped at k.  stats()[3] then holds the levels: the distinct edge values.  The
+     * per-edge list is a C-ABI call (tgo_copy_truss_edges).
+     */
+    public static native long[] ktruss(long ctx, int k);
+
+    /**
      * tgo_scc over a bothE load read as a directed graph: every vertex's label, the smallest Titan
      * id of its strongly connected component, in row order; null on failure.  stats()[3] then holds
      * the device launches of the run.
@@ -134,7 +143,7 @@ public final class TgoNative {
     /** tgo_result_kind */
     public static final int RESULT_DISTANCE = 0, RESULT_PAGERANK = 1, RESULT_DEGREE = 2, RESULT_COMPONENT = 4,
             RESULT_TRIANGLES = 5, RESULT_CORE = 6, RESULT_SCC = 7, RESULT_BETWEENNESS = 8,
-            RESULT_PEER_PRESSURE = 9, RESULT_CLOSENESS = 10;
+            RESULT_PEER_PRESSURE = 9, RESULT_CLOSENESS = 10, RESULT_TRUSS = 11;
     /**
      * tgo_result_rows: the edgestore entries (single-cardinality property entries) of the last
      * program's compute keys, as {long[] rowKeys, long[] rowEntryBegin, long[] rowByteBegin,

@@ -10,10 +10,10 @@ from .computer import (  # noqa: F401
     ClosenessCentralityVertexProgram, ClosenessRankMapReduce,
     ClusterCountMapReduce, ClusterPopulationMapReduce, ConnectedComponentVertexProgram, CoreSizeMapReduce,
     DegeneracyMapReduce, DegreeCounter, DegreeMapper, ExecutionException, GpuGraph, GpuGraphComputer,
-    KCoreVertexProgram, KeyValue, PeerPressureVertexProgram,
+    KCoreVertexProgram, KTrussVertexProgram, KeyValue, MaxTrussMapReduce, PeerPressureVertexProgram,
     PageRankMapReduce, PageRankVertexProgram, SccSizeMapReduce, ShortestDistanceMapReduce,
     ShortestDistanceVertexProgram, StronglyConnectedComponentsVertexProgram, TitanGraphComputer, TransitivityMapReduce, TriangleCountMapReduce,
-    TriangleCountVertexProgram,
+    TriangleCountVertexProgram, TrussSizeMapReduce,
 )
 from .generic import (  # noqa: F401
     ComputeKeyMapReduce, EdgeExpr, FulgoraMemory, GenericVertexProgram, MessageScope, Messenger, Vertices,
@@ -30,6 +30,7 @@ __all__ = [
     "ConnectedComponentVertexProgram", "ClusterPopulationMapReduce", "ClusterCountMapReduce",
     "TriangleCountVertexProgram", "TriangleCountMapReduce", "TransitivityMapReduce",
     "KCoreVertexProgram", "DegeneracyMapReduce", "CoreSizeMapReduce",
+    "KTrussVertexProgram", "MaxTrussMapReduce", "TrussSizeMapReduce",
     "StronglyConnectedComponentsVertexProgram", "SccSizeMapReduce",
     "BetweennessCentralityVertexProgram", "BetweennessRankMapReduce",
     "ClosenessCentralityVertexProgram", "ClosenessRankMapReduce",

@@ -38,6 +38,7 @@ RESULT_SCC = 7
 RESULT_BETWEENNESS = 8
 RESULT_PEER_PRESSURE = 9
 RESULT_CLOSENESS = 10
+RESULT_TRUSS = 11
 CC_HOOK, CC_PROPAGATE = 0, 1     # tgo_cc_path
 SSSP_HOP_BOUNDED, SSSP_DELTA = 0, 1
 FLAG_STATS = 1
@@ -171,6 +172,16 @@ class CoreInfo(C.Structure):
                 ("levels", C.c_int32), ("rounds", C.c_int32)]
 
 
+class TrussArgs(C.Structure):
+    _fields_ = [("scope", C.c_int32), ("flags", C.c_int32), ("k", C.c_int32), ("wave_row", C.c_int32),
+                ("block_row", C.c_int32), ("peel_wave_row", C.c_int32)]
+
+
+class TrussInfo(C.Structure):
+    _fields_ = [("max_truss", C.c_int64), ("innermost_edges", C.c_int64), ("triangles", C.c_int64),
+                ("simple_edges", C.c_int64), ("levels", C.c_int32), ("rounds", C.c_int32)]
+
+
 class SccArgs(C.Structure):
     _fields_ = [("scope", C.c_int32), ("flags", C.c_int32)]
 
@@ -235,7 +246,7 @@ EXPORTS = [
     "tgo_gather", "tgo_combine_global", "tgo_dense_ids", "tgo_decode_edge_entry", "tgo_result_rows",
     "tgo_gather_lists", "tgo_result_rows_values", "tgo_set_edge_program",
     "tgo_components", "tgo_copy_components", "tgo_triangles", "tgo_copy_triangles",
-    "tgo_kcore", "tgo_copy_cores", "tgo_scc", "tgo_copy_scc", "tgo_betweenness", "tgo_copy_betweenness",
+    "tgo_kcore", "tgo_copy_cores", "tgo_ktruss", "tgo_copy_truss", "tgo_copy_truss_edges", "tgo_scc", "tgo_copy_scc", "tgo_betweenness", "tgo_copy_betweenness",
     "tgo_peer_pressure", "tgo_copy_peer_pressure", "tgo_closeness", "tgo_copy_closeness",
     "tgo_rmat_edges", "tgo_rmat_edges_device", "tgo_rmat_partition_device", "tgo_pick_roots", "tgo_synth_rows",
     # titan_gpu_olap_part.h (1-D vertex-partitioned multi-GPU)
@@ -299,6 +310,9 @@ def load() -> C.CDLL:
         "tgo_copy_triangles": (C.c_int, [vp, _i64p, _i64p, C.POINTER(C.c_double)]),
         "tgo_kcore": (C.c_int, [vp, P(CoreArgs), _i64p, P(CoreInfo)]),
         "tgo_copy_cores": (C.c_int, [vp, _i64p]),
+        "tgo_ktruss": (C.c_int, [vp, P(TrussArgs), _i64p, P(TrussInfo)]),
+        "tgo_copy_truss": (C.c_int, [vp, _i64p]),
+        "tgo_copy_truss_edges": (C.c_int, [vp, _i64p, _i64p, _i64p, _i64p]),
         "tgo_scc": (C.c_int, [vp, P(SccArgs), _i64p, P(SccInfo)]),
         "tgo_copy_scc": (C.c_int, [vp, _i64p]),
         "tgo_betweenness": (C.c_int, [vp, P(BcArgs), _i64p, C.c_int64, C.POINTER(C.c_double), P(BcInfo)]),

@@ -421,6 +421,38 @@ class KCoreVertexProgram(VertexProgram):
         return KCoreVertexProgram.Builder()
 
 
+class KTrussVertexProgram(VertexProgram):
+    """k-truss decomposition over bothE on the simple undirected projection (tgo_ktruss): parallel
+    edges, the two directions of a pair and self-loops collapse.  TRUSS = the largest truss value of
+    an edge at the vertex (Long): an edge's truss value is the largest k such that it lies in a
+    subgraph whose edges are all in at least k - 2 triangles of that subgraph; 0 without a
+    neighbour.  k >= 2 peels only the levels below k and reports min(truss, k); 0 decomposes fully.
+    memory.getIteration() is the number of distinct edge values (the peel's levels).  The per-edge
+    values stay with the engine (Engine.copy_truss_edges).  Result graph and persist preference as
+    ShortestDistanceVertexProgram."""
+    TRUSS = "titan.kTruss.trussNumber"
+    compute_keys = (TRUSS,)
+    scope_name = "bothE"
+
+    def __init__(self, k=0):
+        self.k = int(k)
+
+    class Builder:
+        def __init__(self):
+            self._k = 0
+
+        def k(self, k):
+            self._k = int(k)
+            return self
+
+        def create(self, graph=None):
+            return KTrussVertexProgram(self._k)
+
+    @staticmethod
+    def build():
+        return KTrussVertexProgram.Builder()
+
+
 class StronglyConnectedComponentsVertexProgram(VertexProgram):
     """Strongly connected components over bothE read as a directed graph (tgo_scc): an arc u -> v
     for every OUT edge of u to v.  COMPONENT = the smallest Titan id among the vertices that the
@@ -761,6 +793,41 @@ class CoreSizeMapReduce(MapReduce):
         return {int(k): int(v) for k, v in zip(u, c)}
 
 
+class MaxTrussMapReduce(MapReduce):
+    """The largest truss number of a vertex (0 without the property)."""
+    DEFAULT_MEMORY_KEY = "maxTruss"
+
+    def __init__(self, key=DEFAULT_MEMORY_KEY):
+        self.memory_key = key
+
+    @staticmethod
+    def build():
+        return _MemoryKeyBuilder(MaxTrussMapReduce)
+
+    def emit(self, ids, props):
+        truss = props.get(KTrussVertexProgram.TRUSS)
+        return 0 if truss is None or len(truss) == 0 else int(np.max(np.asarray(truss, dtype=np.int64)))
+
+
+class TrussSizeMapReduce(MapReduce):
+    """Truss number of a vertex -> number of vertices carrying it."""
+    DEFAULT_MEMORY_KEY = "trussSizes"
+
+    def __init__(self, key=DEFAULT_MEMORY_KEY):
+        self.memory_key = key
+
+    @staticmethod
+    def build():
+        return _MemoryKeyBuilder(TrussSizeMapReduce)
+
+    def emit(self, ids, props):
+        truss = props.get(KTrussVertexProgram.TRUSS)
+        if truss is None:
+            return {}
+        u, c = np.unique(np.asarray(truss, dtype=np.int64), return_counts=True)
+        return {int(k): int(v) for k, v in zip(u, c)}
+
+
 class SccSizeMapReduce(MapReduce):
     """Strongly connected component label -> number of vertices carrying it."""
     DEFAULT_MEMORY_KEY = "sccSizes"
@@ -992,6 +1059,7 @@ class GpuGraphComputer(TitanGraphComputer):
                     TriangleCountVertexProgram: (L.RESULT_TRIANGLES, (TriangleCountVertexProgram.TRIANGLES,
                                                                       TriangleCountVertexProgram.CLUSTERING)),
                     KCoreVertexProgram: (L.RESULT_CORE, (KCoreVertexProgram.CORE,)),
+                    KTrussVertexProgram: (L.RESULT_TRUSS, (KTrussVertexProgram.TRUSS,)),
                     StronglyConnectedComponentsVertexProgram: (L.RESULT_SCC,
                                                                (StronglyConnectedComponentsVertexProgram.COMPONENT,)),
                     BetweennessCentralityVertexProgram: (L.RESULT_BETWEENNESS,
@@ -1104,6 +1172,11 @@ class GpuGraphComputer(TitanGraphComputer):
         elif isinstance(p, KCoreVertexProgram):
             eng = self.graph.engine_for(L.SCOPE_BOTH_E)
             props[KCoreVertexProgram.CORE], info = eng.kcore()
+            iteration = info["levels"]
+            ids = eng.vertex_ids()
+        elif isinstance(p, KTrussVertexProgram):
+            eng = self.graph.engine_for(L.SCOPE_BOTH_E)
+            props[KTrussVertexProgram.TRUSS], info = eng.ktruss(k=p.k)
             iteration = info["levels"]
             ids = eng.vertex_ids()
         elif isinstance(p, StronglyConnectedComponentsVertexProgram):

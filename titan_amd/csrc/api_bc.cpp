@@ -18,7 +18,9 @@ namespace {
 // Default of TGO_TUNE_BC_WAVE_ROW.
 constexpr int64_t kBcWaveRow = 64;
 
-int bc_simple_adjacency(tgo_ctx* ctx) {
+}  // namespace
+
+int tgo::bc_simple_adjacency(tgo_ctx* ctx) {
     DevGraph& g = ctx->g;
     Scratch& s = ctx->sc;
     hipStream_t st = ctx->stream;
@@ -49,6 +51,8 @@ int bc_simple_adjacency(tgo_ctx* ctx) {
     g.bc_smax = static_cast<int64_t>(longest);
     return TGO_OK;
 }
+
+namespace {
 
 // The lists one run walks: predecessors for sigma, successors for delta.
 struct BcRun {

@@ -279,7 +279,7 @@ static int result_rows_impl(tgo_ctx* ctx, const tgo_result_args* a, const Result
 int tgo_result_rows(tgo_ctx* ctx, const tgo_result_args* a, tgo_result_size* size, const tgo_rows_buf* out) {
     if (!ctx) return TGO_E_INVALID;
     if (!a || !size) return fail(ctx, TGO_E_INVALID, "null args");
-    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_CLOSENESS || a->kind == TGO_RESULT_VALUES)
+    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_TRUSS || a->kind == TGO_RESULT_VALUES)
         return fail(ctx, TGO_E_INVALID, "invalid result kind");
     if (ctx->res_kind != a->kind)
         return fail(ctx, TGO_E_STATE, "no finished program of that kind is the last one run on this ctx");
@@ -295,6 +295,10 @@ int tgo_result_rows(tgo_ctx* ctx, const tgo_result_args* a, tgo_result_size* siz
     if (a->kind == TGO_RESULT_CORE && a->datatypes[0] != TGO_DT_LONG && a->datatypes[0] != TGO_DT_INTEGER &&
         a->datatypes[0] != TGO_DT_OBJECT)
         return fail(ctx, TGO_E_INVALID, "the core number's compute key must be Long, Integer or generic (Object)");
+    // a truss value is at most d(v) + 1 < 2^31: as the core number
+    if (a->kind == TGO_RESULT_TRUSS && a->datatypes[0] != TGO_DT_LONG && a->datatypes[0] != TGO_DT_INTEGER &&
+        a->datatypes[0] != TGO_DT_OBJECT)
+        return fail(ctx, TGO_E_INVALID, "the truss number's compute key must be Long, Integer or generic (Object)");
     if ((a->kind == TGO_RESULT_SCC || a->kind == TGO_RESULT_PEER_PRESSURE) && a->datatypes[0] != TGO_DT_LONG && a->datatypes[0] != TGO_DT_INTEGER &&
         a->datatypes[0] != TGO_DT_OBJECT)
         return fail(ctx, TGO_E_INVALID, "the component label's compute key must be Long, Integer or generic (Object)");

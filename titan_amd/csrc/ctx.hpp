@@ -342,6 +342,11 @@ int titan_ids_by_index(tgo_ctx* ctx);
 // tgo_triangles and tgo_kcore walk them.
 int tri_forward_lists(tgo_ctx* ctx);
 
+// ------------------------------------------------------------------ api_bc.cpp
+// The sorted simple adjacency of the undirected projection (g.bc_s*), built once per graph (the caller
+// checks g.bc_sadj and n > 0): tgo_betweenness and tgo_ktruss walk it.
+int bc_simple_adjacency(tgo_ctx* ctx);
+
 // ------------------------------------------------------------------ api_msbfs.cpp
 int ms_alloc(tgo_ctx* ctx);
 double ms_split_of(const tgo_ctx* ctx);

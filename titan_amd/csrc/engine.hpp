@@ -486,6 +486,16 @@ struct DevGraph {
     int64_t* bc_soff = nullptr;     // n + 1
     int32_t* bc_sadj = nullptr;     // bc_snnz
     int64_t bc_snnz = 0, bc_smax = 0;   // its entries and its longest row
+    // k-truss (tgo_ktruss, built on its first run): a simple edge's id is its position in tri_fadj
+    int32_t* truss_seid = nullptr;  // bc_snnz: the edge id of every entry of bc_sadj
+    int32_t* truss_erow = nullptr;  // tri_fnnz: the row of tri_fadj that holds the edge (its larger endpoint)
+    int32_t* truss_sup0 = nullptr;  // tri_fnnz: the triangles through the edge (the last run's support pass)
+    int32_t* truss_sup = nullptr;   // tri_fnnz: the peel's working support
+    int32_t* truss_tr = nullptr;    // tri_fnnz: 0 alive, -1 in the frontier, else the edge's truss value
+    int32_t* truss_q = nullptr;     // 4 x tri_fnnz: two level queues, two alive lists; after a run its first
+                                    // 8 x tri_fnnz bytes stage a column of tgo_copy_truss_edges
+    unsigned long long* truss_tot = nullptr; // 16 words per run: [0..3] the support pass's row queues and tickets,
+                                    // [4] edges at the largest value, [5] that value, [6] sum of the supports
     // ranks of the Titan ids among the executed vertices (tgo_peer_pressure, built on its first run)
     int32_t* pp_rank = nullptr;     // n: internal index -> rank
     int32_t* pp_inv = nullptr;      // n: rank -> internal index
@@ -985,6 +995,44 @@ hipError_t k_core_tail(const int32_t* list, int64_t len, const CoreView& g, int3
                        Counters* cnt, hipStream_t s);
 hipError_t k_core_finish(const int32_t* deg, int64_t n, int32_t top, int64_t* core, unsigned long long* tot,
                          hipStream_t s);
+
+// k-truss decomposition (truss.hip).  Lists: k_truss_edge_rows writes erow (the row of every forward
+// entry), k_truss_seid the edge id of every entry of the simple adjacency (*err raised when the two
+// lists disagree).  k_truss_support adds every triangle to the support of its three edges (sup: one
+// int32 per forward entry, zero before; row classes and queues as k_tri_count).  k_truss_scan (level l
+// over the alive list; list null = every edge; queue null = none): the cnt->qlen alive edges with
+// sup <= l to queue (marked -1 in tr), with keep the cnt->mf others to keep, cnt->red[0] = INT32_MAX -
+// the smallest sup > l (0: none).  k_truss_peel (one sub-round of level l): the edges that drop to the
+// level to next (cnt->qlen), cnt->red[0] as above over the supports it lowered, cnt->err on a full
+// queue.  k_truss_settle: the sub-round's edges are final at `value`, next's edges the frontier.
+// k_truss_clamp: every alive edge gets `value`.  k_truss_vertex: a vertex's largest edge value.
+// k_truss_totals: tot[0] += edges at top, tot[1] = max value, tot[2] += sum sup0.
+// k_truss_edge_column: column `which` of the edge result (0 / 1 the smaller / larger Titan id, 2 truss,
+// 3 support).
+struct TrussView {
+    const int64_t* foff; const int32_t* fadj;
+    const int64_t* soff; const int32_t* sadj;
+    const int32_t* seid; const int32_t* erow;
+};
+hipError_t k_truss_edge_rows(const int64_t* foff, int64_t n, int32_t* erow, hipStream_t s);
+hipError_t k_truss_seid(const int64_t* soff, const int32_t* sadj, int64_t n, int64_t snnz, const int64_t* foff,
+                        const int32_t* fadj, int32_t* seid, unsigned long long* err, hipStream_t s);
+hipError_t k_truss_support(const int64_t* foff, const int32_t* fadj, int64_t n, int64_t wave_row, int64_t block_row,
+                           int64_t max_fwd, int32_t* sup, int32_t* blist, int32_t* wlist, unsigned long long* q,
+                           hipStream_t s);
+hipError_t k_truss_scan(const int32_t* list, int64_t len, const int32_t* sup, int32_t* tr, int32_t l, int32_t* queue,
+                        int32_t* keep, Counters* cnt, hipStream_t s);
+hipError_t k_truss_peel(const int32_t* cur, int64_t qlen, const TrussView& g, int32_t* sup, const int32_t* tr, int32_t l,
+                        int64_t wave_row, int32_t* next, int64_t m, Counters* cnt, hipStream_t s);
+hipError_t k_truss_settle(const int32_t* cur, int64_t qlen, int32_t value, const int32_t* next, int64_t nlen, int32_t* tr,
+                          hipStream_t s);
+hipError_t k_truss_clamp(int32_t* tr, int64_t m, int32_t value, hipStream_t s);
+hipError_t k_truss_vertex(const int64_t* soff, const int32_t* seid, const int32_t* tr, int64_t n, int64_t* vtruss,
+                          hipStream_t s);
+hipError_t k_truss_totals(const int32_t* tr, const int32_t* sup0, int64_t m, int32_t top, unsigned long long* tot,
+                          hipStream_t s);
+hipError_t k_truss_edge_column(int which, const int32_t* erow, const int32_t* fadj, const int64_t* tid, const int32_t* tr,
+                               const int32_t* sup0, int64_t m, int64_t* out, hipStream_t s);
 
 // Strongly connected components (scc.hip).  SccState over internal ids: comp = -1 while live, else
 // the representative; din / dout = live neighbours' entries other than self; colour / mark as the

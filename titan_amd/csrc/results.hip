@@ -75,7 +75,8 @@ __device__ inline bool value_of(const ResArgs& a, const void* v0, const void* v1
         return true;
     }
     if (a.kind == TGO_RESULT_COMPONENT || a.kind == TGO_RESULT_CORE || a.kind == TGO_RESULT_SCC ||
-        a.kind == TGO_RESULT_BETWEENNESS || a.kind == TGO_RESULT_PEER_PRESSURE) {   // a label / core number / centrality (raw bits) on every executed vertex
+        a.kind == TGO_RESULT_BETWEENNESS || a.kind == TGO_RESULT_PEER_PRESSURE ||
+        a.kind == TGO_RESULT_TRUSS) {   // a label / core or truss number / centrality (raw bits) on every executed vertex
         bits = static_cast<const uint64_t*>(v0)[v];
         return true;
     }
@@ -187,18 +188,18 @@ int encode_results(const ResultSource& src, const tgo_result_args* a, const int3
     ra.kind = a->kind;
     ra.nkeys = a->kind == TGO_RESULT_PAGERANK || a->kind == TGO_RESULT_TRIANGLES || a->kind == TGO_RESULT_CLOSENESS ? 2 : 1;
     ra.rel_base = a->relation_id_base;
-    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_CLOSENESS) { err = "unknown result kind"; return TGO_E_INVALID; }
-    int want[11][2] = {{TGO_DT_LONG, 0}, {TGO_DT_DOUBLE, TGO_DT_DOUBLE}, {TGO_DT_INTEGER, 0}, {0, 0}, {TGO_DT_LONG, 0},
+    if (a->kind < TGO_RESULT_DISTANCE || a->kind > TGO_RESULT_TRUSS) { err = "unknown result kind"; return TGO_E_INVALID; }
+    int want[12][2] = {{TGO_DT_LONG, 0}, {TGO_DT_DOUBLE, TGO_DT_DOUBLE}, {TGO_DT_INTEGER, 0}, {0, 0}, {TGO_DT_LONG, 0},
                        {TGO_DT_LONG, TGO_DT_DOUBLE}, {TGO_DT_LONG, 0}, {TGO_DT_LONG, 0}, {TGO_DT_DOUBLE, 0}, {TGO_DT_LONG, 0},
-                       {TGO_DT_DOUBLE, TGO_DT_DOUBLE}};
+                       {TGO_DT_DOUBLE, TGO_DT_DOUBLE}, {TGO_DT_LONG, 0}};
     // StandardSerializer registration numbers of the value classes (:71-81): Long 13, Double 20, Integer 12
     // (per key where a kind's two keys differ: the triangle count is a Long, its coefficient a Double)
-    uint8_t reg[11][2] = {{0x80 | 13, 0}, {0x80 | 20, 0x80 | 20}, {0x80 | 12, 0}, {0, 0}, {0x80 | 13, 0},
+    uint8_t reg[12][2] = {{0x80 | 13, 0}, {0x80 | 20, 0x80 | 20}, {0x80 | 12, 0}, {0, 0}, {0x80 | 13, 0},
                           {0x80 | 13, 0x80 | 20}, {0x80 | 13, 0}, {0x80 | 13, 0}, {0x80 | 20, 0}, {0x80 | 13, 0},
-                          {0x80 | 20, 0x80 | 20}};
-    static_assert(TGO_RESULT_CLOSENESS == 10, "want / reg hold one row per result kind");
+                          {0x80 | 20, 0x80 | 20}, {0x80 | 13, 0}};
+    static_assert(TGO_RESULT_TRUSS == 11, "want / reg hold one row per result kind");
     const bool long_or_int = a->kind == TGO_RESULT_COMPONENT || a->kind == TGO_RESULT_TRIANGLES || a->kind == TGO_RESULT_CORE ||
-                             a->kind == TGO_RESULT_SCC || a->kind == TGO_RESULT_PEER_PRESSURE;
+                             a->kind == TGO_RESULT_SCC || a->kind == TGO_RESULT_PEER_PRESSURE || a->kind == TGO_RESULT_TRUSS;
     if (long_or_int) {
         // the labels / counts / core numbers are longs: a Long key, an Integer key (the caller checked the range)
         // or a generic key holding Longs — the int64 encoder of a generic program's values

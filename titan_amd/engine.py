@@ -391,6 +391,38 @@ class Engine:
         _check(self.lib, self.ctx, self.lib.tgo_copy_cores(self.ctx, L.ptr(out, C.c_int64)))
         return out
 
+    def ktruss(self, k=0, fetch=True, wave_row=0, block_row=0, peel_wave_row=0):
+        """k-truss decomposition of a bothE load over its simple undirected projection (tgo_ktruss):
+        (vtruss, info) — vtruss[v] = the largest truss value of an edge at v, in row order, 0 without
+        a neighbour (None when fetch is False: the result stays on the device for copy_truss /
+        copy_truss_edges / result_rows); info = dict(max_truss, innermost_edges, triangles,
+        simple_edges, levels, rounds).  k >= 2 peels only the levels below k and reports
+        min(truss, k).  wave_row, block_row and peel_wave_row move work between the kernels' paths
+        (0: the default) and never change a value.  rounds (peel launches) is a diagnostic."""
+        a = L.TrussArgs(L.SCOPE_BOTH_E, 0, k, wave_row, block_row, peel_wave_row)
+        info = L.TrussInfo()
+        out = np.zeros(self.n, dtype=np.int64) if fetch else None
+        _check(self.lib, self.ctx, self.lib.tgo_ktruss(self.ctx, C.byref(a), L.ptr(out, C.c_int64), C.byref(info)))
+        self._truss_edges = int(info.simple_edges)
+        return out, {"max_truss": int(info.max_truss), "innermost_edges": int(info.innermost_edges),
+                     "triangles": int(info.triangles), "simple_edges": int(info.simple_edges),
+                     "levels": int(info.levels), "rounds": int(info.rounds)}
+
+    def copy_truss(self):
+        """The per-vertex truss numbers of the last ktruss() run, in row order."""
+        out = np.zeros(self.n, dtype=np.int64)
+        _check(self.lib, self.ctx, self.lib.tgo_copy_truss(self.ctx, L.ptr(out, C.c_int64)))
+        return out
+
+    def copy_truss_edges(self):
+        """The per-edge result of the last ktruss() run: (u, v, truss, support), one entry per simple
+        edge, Titan ids with u < v; the order is the load's own (the same from run to run)."""
+        m = getattr(self, "_truss_edges", 0)
+        u, v, t, s = (np.zeros(m, dtype=np.int64) for _ in range(4))
+        _check(self.lib, self.ctx, self.lib.tgo_copy_truss_edges(self.ctx, L.ptr(u, C.c_int64), L.ptr(v, C.c_int64),
+                                                                 L.ptr(t, C.c_int64), L.ptr(s, C.c_int64)))
+        return u, v, t, s
+
     def scc(self, fetch=True):
         """Strongly connected components of a bothE load read as a directed graph (tgo_scc): an arc
         u -> v for every OUT entry of u that names v.  (labels, info) — labels[v] = the smallest
