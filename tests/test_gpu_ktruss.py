@@ -189,6 +189,54 @@ def test_every_path_gives_the_same_bytes(graph, rmat10):
     check(eng, ref)
 
 
+# ------------------------------------------------------------------ one walk, two credit policies
+def gnp64_and_an_isolated_vertex():
+    """65 vertices: a ragged last word of rows, and rows of fewer than two forward entries."""
+    s, d = np.triu_indices(64, 1)
+    rng = np.random.default_rng(65)
+    keep = rng.random(len(s)) < 0.3
+    flip = rng.random(len(s)) < 0.5
+    s, d = s[keep], d[keep]
+    flip = flip[keep]
+    return 65, np.where(flip, d, s).astype(np.int32), np.where(flip, s, d).astype(np.int32)
+
+
+@pytest.fixture(scope="module")
+def walk_graphs(rmat10):
+    graphs = {"clique70": kr.clique(70),                # forward rows of up to 69 entries: one past a wave
+              "rmat10": rmat10[:3],
+              "gnp64+1": gnp64_and_an_isolated_vertex()}
+    return {name: (g, tri_reference(*g)[0]) for name, g in graphs.items()}
+
+
+FAR = 10**6                                             # a row length above every forward row
+ROW_CLASSES = {"lane": (FAR, FAR), "wave": (1, FAR), "block": (FAR, 2)}     # (wave_row, block_row)
+
+
+@pytest.mark.parametrize("rows", list(ROW_CLASSES))
+@pytest.mark.parametrize("graph", ["clique70", "rmat10", "gnp64+1"])
+def test_edge_credits_sum_to_vertex_credits(graph, rows, walk_graphs):
+    """tgo_ktruss's supports and tgo_triangles' counts come from one enumeration: per vertex, the
+    supports of its edges add up to twice its triangles, whichever kernel walks the rows."""
+    (n, src, dst), tri_ref = walk_graphs[graph]
+    wave_row, block_row = ROW_CLASSES[rows]
+    eng = Engine().load_edges(n, src, dst, BOTH)
+    eng.set_tuning(L.TUNE_TRI_WAVE_ROW, wave_row).set_tuning(L.TUNE_TRI_BLOCK_ROW, block_row)
+    _, tinfo = eng.triangles(fetch=False)
+    tri = eng.copy_triangles()[0]
+    assert tri_ref.any() and np.array_equal(tri, tri_ref)           # (not zero on both sides)
+    _, info = eng.ktruss(wave_row=wave_row, block_row=block_row)
+    u, v, _, sup = eng.copy_truss_edges()
+    ids = eng.vertex_ids()
+    order = np.argsort(ids)
+    at = lambda x: order[np.searchsorted(ids[order], x)]             # the row of a Titan id
+    per_vertex = np.zeros(n, np.int64)
+    np.add.at(per_vertex, at(u), sup)
+    np.add.at(per_vertex, at(v), sup)
+    assert np.array_equal(per_vertex, 2 * tri)
+    assert info["triangles"] == tinfo["triangles"]
+
+
 # ------------------------------------------------------------------ k
 def test_k_clamps_and_stops_the_peel(rmat10):
     n, src, dst, ref = rmat10

@@ -72,31 +72,25 @@ int core_peel_levels(tgo_ctx* ctx, const CoreArrays& A, int32_t& levels, int32_t
     const int64_t tail = std::min<int64_t>(tuned(ctx->tune.i64(TGO_TUNE_CORE_TAIL), kCoreTail), kCoreQueue);
     const int64_t lds_cap = tuned(ctx->tune.i64(TGO_TUNE_CORE_LDS_QUEUE), kCoreLdsQueue);
     int32_t* const deg = A.deg;
-    auto min_of = [](unsigned long long word) {        // Counters::red[0] of core_scan / core_peel
-        return word ? static_cast<int64_t>(INT32_MAX) - static_cast<int64_t>(word) : INT64_MAX;
-    };
     int rc = TGO_OK;
     HIP_TRY(k_core_deg_init(g.tri_deg, n, deg, st));
     HIP_TRY(k_level_prep(s.cnt, nullptr, 0, nullptr, st));
     // the smallest degree: a scan that queues nothing
     HIP_TRY(k_core_scan(nullptr, n, deg, -1, nullptr, nullptr, s.cnt, st));
     if ((rc = turn_checked(ctx, kPeel))) return rc;
-    int64_t next_k = min_of(s.hcnt->red[0]);
-    int64_t alive = n, len = n, k = -1;
-    const int32_t* list = nullptr;      // the alive list in use (null: every vertex)
-    int spare = 0;                      // the alive_list buffer it is not in
+    int64_t next_k = level_min(s.hcnt->red[0]);
+    int64_t alive = n, k = -1;
+    AliveList al(n, A.alive_list[0], A.alive_list[1]);
     while (alive > 0) {
         if (next_k == INT64_MAX) return fail(ctx, TGO_E_HIP, "k-core peel: alive vertices without a degree");
         if (tail > 0 && alive <= tail) {
-            if (len > 2 * alive) {      // the one workgroup scans the list once per level: compact it first
-                HIP_TRY(k_core_scan(list, len, deg, static_cast<int32_t>(k), nullptr, A.alive_list[spare], s.cnt, st));
+            if (al.len > 2 * alive) {   // the one workgroup scans the list once per level: compact it first
+                HIP_TRY(k_core_scan(al.list, al.len, deg, static_cast<int32_t>(k), nullptr, al.keep_buffer(), s.cnt, st));
                 if ((rc = turn_checked(ctx, kPeel))) return rc;
-                list = A.alive_list[spare];
-                spare ^= 1;
-                len = static_cast<int64_t>(s.hcnt->mf);
-                if (len != alive) return fail(ctx, TGO_E_HIP, "k-core peel: inconsistent alive count");
+                al.adopt(static_cast<int64_t>(s.hcnt->mf));
+                if (al.len != alive) return fail(ctx, TGO_E_HIP, "k-core peel: inconsistent alive count");
             }
-            HIP_TRY(k_core_tail(list, len, lists, deg, static_cast<int32_t>(k), wave_row, s.cnt, st));
+            HIP_TRY(k_core_tail(al.list, al.len, lists, deg, static_cast<int32_t>(k), wave_row, s.cnt, st));
             if ((rc = turn_checked(ctx, kPeel))) return rc;
             ++rounds;
             levels += static_cast<int32_t>(s.hcnt->qlen);
@@ -105,17 +99,13 @@ int core_peel_levels(tgo_ctx* ctx, const CoreArrays& A, int32_t& levels, int32_t
             return TGO_OK;
         }
         k = next_k;
-        const bool rebuild = 2 * alive <= len;      // the list has at least halved
-        HIP_TRY(k_core_scan(list, len, deg, static_cast<int32_t>(k), A.queue[0], rebuild ? A.alive_list[spare] : nullptr,
+        const bool rebuild = al.wants_rebuild(alive);
+        HIP_TRY(k_core_scan(al.list, al.len, deg, static_cast<int32_t>(k), A.queue[0], rebuild ? al.keep_buffer() : nullptr,
                             s.cnt, st));
         if ((rc = turn_checked(ctx, kPeel))) return rc;
         int64_t qlen = static_cast<int64_t>(s.hcnt->qlen);
-        next_k = min_of(s.hcnt->red[0]);
-        if (rebuild) {
-            list = A.alive_list[spare];
-            spare ^= 1;
-            len = static_cast<int64_t>(s.hcnt->mf);
-        }
+        next_k = level_min(s.hcnt->red[0]);
+        if (rebuild) al.adopt(static_cast<int64_t>(s.hcnt->mf));
         // the minimum named a vertex that the level before went on to drop and peel: nobody is
         // left at k, and this scan's minimum is exact (nothing has changed since it ran)
         if (qlen == 0) continue;
@@ -134,7 +124,7 @@ int core_peel_levels(tgo_ctx* ctx, const CoreArrays& A, int32_t& levels, int32_t
             if (drops > alive || qlen > drops) return fail(ctx, TGO_E_HIP, "k-core peel: inconsistent drop count");
             innermost += drops;
             alive -= drops;
-            next_k = std::min(next_k, min_of(s.hcnt->red[0]));
+            next_k = std::min(next_k, level_min(s.hcnt->red[0]));
         }
     }
     return TGO_OK;

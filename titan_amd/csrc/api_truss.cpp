@@ -77,9 +77,6 @@ int truss_peel_levels(tgo_ctx* ctx, const TrussArrays& A, int64_t stop, int64_t 
     hipStream_t st = ctx->stream;
     const int64_t m = g.tri_fnnz;
     const TrussView lists{g.tri_foff, g.tri_fadj, g.bc_soff, g.bc_sadj, g.truss_seid, g.truss_erow};
-    auto min_of = [](unsigned long long word) {        // Counters::red[0] of truss_scan / truss_peel
-        return word ? static_cast<int64_t>(INT32_MAX) - static_cast<int64_t>(word) : INT64_MAX;
-    };
     int rc = TGO_OK;
     HIP_TRY(hipMemcpyAsync(A.sup, A.sup0, m * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemsetAsync(A.tr, 0, m * sizeof(int32_t), st));
@@ -87,25 +84,20 @@ int truss_peel_levels(tgo_ctx* ctx, const TrussArrays& A, int64_t stop, int64_t 
     // the smallest support: a scan that queues nothing
     HIP_TRY(k_truss_scan(nullptr, m, A.sup, A.tr, -1, nullptr, nullptr, s.cnt, st));
     if ((rc = turn_checked(ctx, kPeel))) return rc;
-    int64_t next_l = min_of(s.hcnt->red[0]);
-    int64_t alive = m, len = m;
-    const int32_t* list = nullptr;      // the alive list in use (null: every edge)
-    int spare = 0;                      // the alive_list buffer it is not in
+    int64_t next_l = level_min(s.hcnt->red[0]);
+    int64_t alive = m;
+    AliveList al(m, A.alive_list[0], A.alive_list[1]);
     while (alive > 0) {
         if (next_l == INT64_MAX) return fail(ctx, TGO_E_HIP, "k-truss peel: alive edges without a support");
         if (stop >= 0 && next_l >= stop) break;
         const int64_t l = next_l;
-        const bool rebuild = 2 * alive <= len;      // the list has at least halved
-        HIP_TRY(k_truss_scan(list, len, A.sup, A.tr, static_cast<int32_t>(l), A.queue[0],
-                             rebuild ? A.alive_list[spare] : nullptr, s.cnt, st));
+        const bool rebuild = al.wants_rebuild(alive);
+        HIP_TRY(k_truss_scan(al.list, al.len, A.sup, A.tr, static_cast<int32_t>(l), A.queue[0],
+                             rebuild ? al.keep_buffer() : nullptr, s.cnt, st));
         if ((rc = turn_checked(ctx, kPeel))) return rc;
         int64_t qlen = static_cast<int64_t>(s.hcnt->qlen);
-        next_l = min_of(s.hcnt->red[0]);
-        if (rebuild) {
-            list = A.alive_list[spare];
-            spare ^= 1;
-            len = static_cast<int64_t>(s.hcnt->mf);
-        }
+        next_l = level_min(s.hcnt->red[0]);
+        if (rebuild) al.adopt(static_cast<int64_t>(s.hcnt->mf));
         // the minimum named an edge that the level before went on to drop and peel: nobody is left
         // at l, and this scan's minimum is exact (nothing has changed since it ran)
         if (qlen == 0) continue;
@@ -123,7 +115,7 @@ int truss_peel_levels(tgo_ctx* ctx, const TrussArrays& A, int64_t stop, int64_t 
                 ++rounds;
                 nlen = static_cast<int64_t>(s.hcnt->qlen);
                 if (nlen > alive) return fail(ctx, TGO_E_HIP, "k-truss peel: inconsistent drop count");
-                next_l = std::min(next_l, min_of(s.hcnt->red[0]));
+                next_l = std::min(next_l, level_min(s.hcnt->red[0]));
             }
             HIP_TRY(k_truss_settle(A.queue[cur], qlen, static_cast<int32_t>(l + 2), A.queue[cur ^ 1], nlen, A.tr, st));
             innermost += nlen;

@@ -31,19 +31,11 @@
 // rounding, not bit for bit.  A sigma beyond the finite range raises Counters::err.
 // No grid barrier, no spin.  Wave = 64 lanes.
 #include <hip/hip_runtime.h>
-#include <algorithm>
-#include <climits>
-#include "frontier.hpp"
+#include "engine.hpp"
+#include "wave.hpp"
 
 namespace tgo {
 namespace {
-
-using u64 = unsigned long long;
-
-inline int bc_grid(int64_t work, int64_t cap = 1 << 16) {
-    const int64_t g = (work + kBlock - 1) / kBlock;
-    return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(g, cap)));
-}
 
 // The same value on every lane: fp64 addition commutes, so both sides of an exchange add alike.
 __device__ __forceinline__ double wave_fold(double x) {
@@ -153,17 +145,8 @@ __global__ void bc_seed(double* sigma, int32_t seed) {
 }
 
 // ---------------------------------------------------------------- the sweeps
-// The calling wave's lanes with `take` set append v to list (one atomicAdd on *count per wave).  A
-// level's slice names a vertex once, so the list (n + 1 entries) cannot overflow.
-__device__ __forceinline__ void wave_append(bool take, int32_t v, int32_t* list, u64* count) {
-    const u64 qm = __ballot(take);
-    if (!qm) return;
-    const int lead = __ffsll(static_cast<long long>(qm)) - 1;
-    u64 base = 0;
-    if (lane() == lead) base = atomicAdd(count, static_cast<u64>(__popcll(qm)));
-    base = __shfl(base, lead, 64);
-    if (take) list[base + __popcll(qm & ((1ULL << lane()) - 1))] = v;
-}
+// The wide rows are queued with wave_append: a level's slice names a vertex once, so the queue
+// (n + 1 entries) cannot overflow.
 
 // The fold of f(tag, u) over the entries u of v's row adj[b, b + l) by one lane, in list order.
 // DEDUP: an entry equal to the one before it or to v is skipped.
@@ -318,21 +301,21 @@ __global__ void __launch_bounds__(kBlock) bc_delta_wave(const int32_t* __restric
 
 hipError_t k_bc_adj_count(const DevCsr& out, const DevCsr& in, int64_t n, int64_t* cnt, unsigned long long* longest,
                           hipStream_t s) {
-    bc_adj_count<<<bc_grid(n + 1), kBlock, 0, s>>>(out.off, out.adj, in.off, in.adj, n, cnt, longest);
+    bc_adj_count<<<grid_for(n + 1, 1 << 16), kBlock, 0, s>>>(out.off, out.adj, in.off, in.adj, n, cnt, longest);
     return hipGetLastError();
 }
 hipError_t k_bc_adj_fill(const DevCsr& out, const DevCsr& in, int64_t n, const int64_t* soff, int32_t* sadj,
                          hipStream_t s) {
-    bc_adj_fill<<<bc_grid(n), kBlock, 0, s>>>(out.off, out.adj, in.off, in.adj, n, soff, sadj);
+    bc_adj_fill<<<grid_for(n, 1 << 16), kBlock, 0, s>>>(out.off, out.adj, in.off, in.adj, n, soff, sadj);
     return hipGetLastError();
 }
 hipError_t k_bc_level_count(const int32_t* level, int64_t n, int32_t depth, int64_t* hist, Counters* cnt, hipStream_t s) {
-    bc_level_count<<<bc_grid(n, 2048), kBlock, 0, s>>>(level, n, depth, reinterpret_cast<u64*>(hist), &cnt->err);
+    bc_level_count<<<grid_for(n, 2048), kBlock, 0, s>>>(level, n, depth, reinterpret_cast<u64*>(hist), &cnt->err);
     return hipGetLastError();
 }
 hipError_t k_bc_level_scatter(const int32_t* level, int64_t n, int32_t depth, int64_t* cursor, int32_t* order,
                               Counters* cnt, hipStream_t s) {
-    bc_level_scatter<<<bc_grid(n, 2048), kBlock, 0, s>>>(level, n, depth, reinterpret_cast<u64*>(cursor), order, &cnt->err);
+    bc_level_scatter<<<grid_for(n, 2048), kBlock, 0, s>>>(level, n, depth, reinterpret_cast<u64*>(cursor), order, &cnt->err);
     return hipGetLastError();
 }
 hipError_t k_bc_seed(double* sigma, int32_t seed, hipStream_t s) {
@@ -348,8 +331,8 @@ hipError_t k_bc_sigma(const int32_t* list, int64_t len, const int64_t* off, cons
                       bool long_rows, Counters* cnt, hipStream_t s) {
     if (len <= 0) return hipSuccess;
     u64* const qc = reinterpret_cast<u64*>(qcount);
-    if (dedup) bc_sigma<true><<<bc_grid(len), kBlock, 0, s>>>(list, len, off, adj, level, L, sigma, wave_row, queue, qc, &cnt->err);
-    else bc_sigma<false><<<bc_grid(len), kBlock, 0, s>>>(list, len, off, adj, level, L, sigma, wave_row, queue, qc, &cnt->err);
+    if (dedup) bc_sigma<true><<<grid_for(len, 1 << 16), kBlock, 0, s>>>(list, len, off, adj, level, L, sigma, wave_row, queue, qc, &cnt->err);
+    else bc_sigma<false><<<grid_for(len, 1 << 16), kBlock, 0, s>>>(list, len, off, adj, level, L, sigma, wave_row, queue, qc, &cnt->err);
     if (!long_rows) return hipGetLastError();
     if (dedup) bc_sigma_wave<true><<<bc_wave_grid(len), kBlock, 0, s>>>(queue, qc, off, adj, level, L, sigma, &cnt->err);
     else bc_sigma_wave<false><<<bc_wave_grid(len), kBlock, 0, s>>>(queue, qc, off, adj, level, L, sigma, &cnt->err);
@@ -360,8 +343,8 @@ hipError_t k_bc_delta(const int32_t* list, int64_t len, const int64_t* off, cons
                       int32_t* queue, int64_t* qcount, bool long_rows, hipStream_t s) {
     if (len <= 0) return hipSuccess;
     u64* const qc = reinterpret_cast<u64*>(qcount);
-    if (dedup) bc_delta<true><<<bc_grid(len), kBlock, 0, s>>>(list, len, off, adj, level, L, sigma, delta, bc, wave_row, queue, qc);
-    else bc_delta<false><<<bc_grid(len), kBlock, 0, s>>>(list, len, off, adj, level, L, sigma, delta, bc, wave_row, queue, qc);
+    if (dedup) bc_delta<true><<<grid_for(len, 1 << 16), kBlock, 0, s>>>(list, len, off, adj, level, L, sigma, delta, bc, wave_row, queue, qc);
+    else bc_delta<false><<<grid_for(len, 1 << 16), kBlock, 0, s>>>(list, len, off, adj, level, L, sigma, delta, bc, wave_row, queue, qc);
     if (!long_rows) return hipGetLastError();
     if (dedup) bc_delta_wave<true><<<bc_wave_grid(len), kBlock, 0, s>>>(queue, qc, off, adj, level, L, sigma, delta, bc);
     else bc_delta_wave<false><<<bc_wave_grid(len), kBlock, 0, s>>>(queue, qc, off, adj, level, L, sigma, delta, bc);

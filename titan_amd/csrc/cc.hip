@@ -21,18 +21,14 @@
 // ids are degree-grouped, so a wave's rows are alike), a row of up to kSerialRow entries walked
 // by its own lane, a longer one by the whole wave, 64 entries a trip.  Wave = 64 lanes.
 #include <hip/hip_runtime.h>
-#include "frontier.hpp"
+#include "engine.hpp"
+#include "wave.hpp"
 
 namespace tgo {
 namespace {
 
 constexpr int64_t kSerialRow = 32;
 constexpr int kJump = 32;           // parents a lane follows per pointer-jumping launch
-
-inline int cc_grid(int64_t work, int cap = 2048) {
-    int64_t g = (work + kBlock - 1) / kBlock;
-    return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(g, cap)));
-}
 
 __device__ __forceinline__ int32_t cas_parent(int32_t* p, int32_t expect, int32_t want) {
     __hip_atomic_compare_exchange_strong(p, &expect, want, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -69,32 +65,23 @@ __global__ void cc_init(int32_t* parent, int64_t n) {
 // Hook the entries [from, to) of every row of list `off/adj` (to < 0: to the row's end).
 __global__ void __launch_bounds__(kBlock) cc_hook(const int64_t* __restrict__ off, const int32_t* __restrict__ adj,
                                                   int64_t n, int64_t from, int64_t to, int32_t* parent) {
-    const int64_t words = (n + 63) >> 6;
-    for (int64_t b = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock; b < words;
-         b += static_cast<int64_t>(gridDim.x) * kWavesPerBlock) {
-        const int64_t wd = b + (threadIdx.x >> 6);
-        const int64_t v = (wd << 6) + lane();
+    for_each_row_64(n, [&](int64_t v, bool live) {
         int64_t kb = 0, ke = 0;
-        if (wd < words && v < n) {
+        if (live) {
             kb = off[v];
             ke = off[v + 1];
             if (to >= 0) ke = min(ke, kb + to);
             kb = min(ke, kb + from);
         }
-        const int64_t deg = ke - kb;
-        if (deg > 0 && deg <= kSerialRow) {
+        lane_or_wave(ke - kb > kSerialRow, [&] {
             int32_t a = static_cast<int32_t>(v);
             for (int64_t k = kb; k < ke; ++k) a = link(parent, a, adj[k]);
-        }
-        unsigned long long big = __ballot(deg > kSerialRow);
-        while (big) {
-            const int src = __ffsll(static_cast<long long>(big)) - 1;
-            big &= big - 1;
+        }, [&](int src) {
             const int64_t bb = __shfl(kb, src, 64), ee = __shfl(ke, src, 64);
-            int32_t a = static_cast<int32_t>((wd << 6) + src);
+            int32_t a = static_cast<int32_t>(v - lane() + src);
             for (int64_t k = bb + lane(); k < ee; k += 64) a = link(parent, a, adj[k]);
-        }
-    }
+        });
+    });
 }
 
 // Pointer jumping: every vertex moves under the ancestor kJump parents up (a root at the latest).
@@ -123,15 +110,6 @@ __global__ void cc_scatter_ids(const int64_t* __restrict__ row_ids, const int32_
         tid[perm[r]] = row_ids[r];
 }
 
-__device__ __forceinline__ long long wave_min_i64(long long x) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const long long y = __shfl_xor(x, d, 64);
-        x = y < x ? y : x;
-    }
-    return x;
-}
-
 // minid[root] = min Titan id of the tree (parent[] is flat: every vertex sits under its root).
 // Lanes of a wave that share a root fold their ids first — on a power-law graph nearly every lane
 // is in the giant component, whose root word would otherwise take one atomic per vertex.
@@ -149,7 +127,7 @@ __global__ void __launch_bounds__(kBlock) cc_min_id(const int32_t* __restrict__ 
             const int lead = __ffsll(static_cast<long long>(m)) - 1;
             const int32_t r0 = __shfl(r, lead, 64);
             const bool mine = todo && r == r0;
-            const long long lo = wave_min_i64(mine ? id : INT64_MAX);
+            const long long lo = wave_min(mine ? id : INT64_MAX);
             if (lane() == lead) atomicMin(&minid[r0], lo);
             if (mine) todo = false;
         }
@@ -165,7 +143,7 @@ __global__ void __launch_bounds__(kBlock) cc_label(const int32_t* __restrict__ p
         label[v] = minid[r];
         mine += r == v;
     }
-    for (int d = 32; d > 0; d >>= 1) mine += __shfl_xor(mine, d, 64);
+    mine = wave_sum(mine);
     if (lane() == 0 && mine) atomicAdd(roots, mine);
 }
 
@@ -174,13 +152,8 @@ __global__ void __launch_bounds__(kBlock) cc_label(const int32_t* __restrict__ p
 // reach v, so labels only fall towards the fixed point, and a round that lowers nothing read
 // nothing stale (a launch starts with cold caches) and proves it.
 __global__ void __launch_bounds__(kBlock) cc_pull_round(View pull, int64_t n, int64_t* label, unsigned long long* changed) {
-    const int64_t words = (n + 63) >> 6;
     bool any = false;
-    for (int64_t b = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock; b < words;
-         b += static_cast<int64_t>(gridDim.x) * kWavesPerBlock) {
-        const int64_t wd = b + (threadIdx.x >> 6);
-        const int64_t v = (wd << 6) + lane();
-        const bool live = wd < words && v < n;
+    for_each_row_64(n, [&](int64_t v, bool live) {
         int64_t b0 = 0, e0 = 0, b1 = 0, e1 = 0;
         if (live) {
             b0 = pull.off0[v]; e0 = pull.off0[v + 1];
@@ -189,28 +162,24 @@ __global__ void __launch_bounds__(kBlock) cc_pull_round(View pull, int64_t n, in
         const int64_t deg = (e0 - b0) + (e1 - b1);
         const int64_t cur = live ? label[v] : 0;
         int64_t m = cur;
-        if (deg <= kSerialRow) {
+        lane_or_wave(deg > kSerialRow, [&] {
             for (int64_t k = b0; k < e0; ++k) m = min(m, label[pull.adj0[k]]);
             for (int64_t k = b1; k < e1; ++k) m = min(m, label[pull.adj1[k]]);
-        }
-        unsigned long long big = __ballot(deg > kSerialRow);
-        while (big) {
-            const int src = __ffsll(static_cast<long long>(big)) - 1;
-            big &= big - 1;
+        }, [&](int src) {
             long long w = INT64_MAX;
             for (int l = 0; l < 2; ++l) {
                 const int64_t bb = __shfl(l == 0 ? b0 : b1, src, 64), ee = __shfl(l == 0 ? e0 : e1, src, 64);
                 const int32_t* adj = l == 0 ? pull.adj0 : pull.adj1;
                 for (int64_t k = bb + lane(); k < ee; k += 64) w = min(w, static_cast<long long>(label[adj[k]]));
             }
-            w = wave_min_i64(w);
+            w = wave_min(w);
             if (lane() == src) m = min(m, static_cast<int64_t>(w));
-        }
+        });
         if (live && m < cur) {
             label[v] = m;
             any = true;
         }
-    }
+    });
     if (__ballot(any) && lane() == 0) atomicAdd(changed, 1ULL);
 }
 
@@ -219,7 +188,7 @@ __global__ void __launch_bounds__(kBlock) cc_count_own(const int64_t* __restrict
     unsigned long long mine = 0;
     for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < n; v += (int64_t)gridDim.x * blockDim.x)
         mine += label[v] == tid[v];
-    for (int d = 32; d > 0; d >>= 1) mine += __shfl_xor(mine, d, 64);
+    mine = wave_sum(mine);
     if (lane() == 0 && mine) atomicAdd(roots, mine);
 }
 
@@ -227,36 +196,36 @@ __global__ void __launch_bounds__(kBlock) cc_count_own(const int64_t* __restrict
 
 // ---------------------------------------------------------------- launchers
 hipError_t k_cc_init(int32_t* parent, int64_t n, hipStream_t s) {
-    cc_init<<<cc_grid(n), kBlock, 0, s>>>(parent, n);
+    cc_init<<<grid_for(n, 2048), kBlock, 0, s>>>(parent, n);
     return hipGetLastError();
 }
 hipError_t k_cc_hook(const DevCsr& list, int64_t n, int64_t from, int64_t to, int32_t* parent, hipStream_t s) {
-    cc_hook<<<cc_grid(((n + 63) / 64) * 64), kBlock, 0, s>>>(list.off, list.adj, n, from, to, parent);
+    cc_hook<<<grid_for(((n + 63) / 64) * 64, 2048), kBlock, 0, s>>>(list.off, list.adj, n, from, to, parent);
     return hipGetLastError();
 }
 hipError_t k_cc_jump(int32_t* parent, int64_t n, unsigned long long* changed, hipStream_t s) {
-    cc_jump<<<cc_grid(n), kBlock, 0, s>>>(parent, n, changed);
+    cc_jump<<<grid_for(n, 2048), kBlock, 0, s>>>(parent, n, changed);
     return hipGetLastError();
 }
 hipError_t k_cc_scatter_ids(const int64_t* row_ids, const int32_t* perm, int64_t* tid, int64_t n, hipStream_t s) {
-    cc_scatter_ids<<<cc_grid(n), kBlock, 0, s>>>(row_ids, perm, tid, n);
+    cc_scatter_ids<<<grid_for(n, 2048), kBlock, 0, s>>>(row_ids, perm, tid, n);
     return hipGetLastError();
 }
 hipError_t k_cc_min_id(const int32_t* parent, const int64_t* tid, int64_t n, int64_t* minid, hipStream_t s) {
-    cc_min_id<<<cc_grid(n), kBlock, 0, s>>>(parent, tid, n, reinterpret_cast<long long*>(minid));
+    cc_min_id<<<grid_for(n, 2048), kBlock, 0, s>>>(parent, tid, n, reinterpret_cast<long long*>(minid));
     return hipGetLastError();
 }
 hipError_t k_cc_label(const int32_t* parent, const int64_t* minid, int64_t n, int64_t* label, unsigned long long* roots,
                       hipStream_t s) {
-    cc_label<<<cc_grid(n), kBlock, 0, s>>>(parent, reinterpret_cast<const long long*>(minid), n, label, roots);
+    cc_label<<<grid_for(n, 2048), kBlock, 0, s>>>(parent, reinterpret_cast<const long long*>(minid), n, label, roots);
     return hipGetLastError();
 }
 hipError_t k_cc_pull_round(const View& pull, int64_t n, int64_t* label, unsigned long long* changed, hipStream_t s) {
-    cc_pull_round<<<cc_grid(((n + 63) / 64) * 64), kBlock, 0, s>>>(pull, n, label, changed);
+    cc_pull_round<<<grid_for(((n + 63) / 64) * 64, 2048), kBlock, 0, s>>>(pull, n, label, changed);
     return hipGetLastError();
 }
 hipError_t k_cc_count_own(const int64_t* label, const int64_t* tid, int64_t n, unsigned long long* roots, hipStream_t s) {
-    cc_count_own<<<cc_grid(n), kBlock, 0, s>>>(label, tid, n, roots);
+    cc_count_own<<<grid_for(n, 2048), kBlock, 0, s>>>(label, tid, n, roots);
     return hipGetLastError();
 }
 

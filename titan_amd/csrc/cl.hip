@@ -26,17 +26,11 @@
 // ecc to row order as int64.  Wave = 64 lanes.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include "frontier.hpp"
+#include "engine.hpp"
+#include "wave.hpp"
 
 namespace tgo {
 namespace {
-
-using u64 = unsigned long long;
-
-inline int cl_grid(int64_t work) {
-    const int64_t g = (work + kBlock - 1) / kBlock;
-    return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(g, 1 << 16)));
-}
 
 template <int NP>
 __global__ void __launch_bounds__(kBlock)
@@ -88,11 +82,8 @@ cl_finish(const u64* __restrict__ far, const u64* __restrict__ reach, const int3
         sum += r;
         top = max(top, static_cast<u64>(ecc[v]));
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        sum += __shfl_xor(sum, d, 64);
-        top = max(top, static_cast<u64>(__shfl_xor(top, d, 64)));
-    }
+    sum = wave_sum(sum);
+    top = wave_max(top);
     __shared__ u64 ssum[kWavesPerBlock], stop[kWavesPerBlock];
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) { ssum[w] = sum; stop[w] = top; }
@@ -115,7 +106,7 @@ template <int NP>
 hipError_t fold_planes(int nplanes, const uint64_t* vis, const uint64_t* planes, int64_t stride, int64_t n, u64* far,
                        u64* reach, int32_t* ecc, double* harm, hipStream_t s) {
     if (nplanes == NP) {
-        cl_fold<NP><<<cl_grid(n), kBlock, 0, s>>>(vis, planes, stride, n, far, reach, ecc, harm);
+        cl_fold<NP><<<grid_for(n, 1 << 16), kBlock, 0, s>>>(vis, planes, stride, n, far, reach, ecc, harm);
         return hipGetLastError();
     }
     if constexpr (NP > 0) return fold_planes<NP - 1>(nplanes, vis, planes, stride, n, far, reach, ecc, harm, s);
@@ -133,13 +124,13 @@ hipError_t k_cl_fold(const uint64_t* vis, LevelPlanes lvl, int nplanes, int64_t 
 hipError_t k_cl_finish(const unsigned long long* far, const unsigned long long* reach, const int32_t* ecc, int64_t n,
                        double* close, unsigned long long* pairs, unsigned long long* deepest, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    cl_finish<<<cl_grid(n), kBlock, 0, s>>>(far, reach, ecc, n, close, pairs, deepest);
+    cl_finish<<<grid_for(n, 1 << 16), kBlock, 0, s>>>(far, reach, ecc, n, close, pairs, deepest);
     return hipGetLastError();
 }
 
 hipError_t k_cl_ecc_rows(const int32_t* ecc, const int32_t* perm, int64_t* out, int64_t n, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    cl_ecc_rows<<<cl_grid(n), kBlock, 0, s>>>(ecc, perm, out, n);
+    cl_ecc_rows<<<grid_for(n, 1 << 16), kBlock, 0, s>>>(ecc, perm, out, n);
     return hipGetLastError();
 }
 

@@ -32,31 +32,11 @@
 // levels of a handful of vertices).  Wave = 64 lanes.  Rows go to lanes as in tri.hip: a row with
 // fewer than wave_row entries is walked by its own lane, a longer one by the whole wave.
 #include <hip/hip_runtime.h>
-#include <algorithm>
-#include <climits>
-#include "frontier.hpp"
+#include "engine.hpp"
+#include "wave.hpp"
 
 namespace tgo {
 namespace {
-
-using u64 = unsigned long long;
-
-inline int core_grid(int64_t work, int64_t cap = 2048) {
-    const int64_t g = (work + kBlock - 1) / kBlock;
-    return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(g, cap)));
-}
-
-__device__ __forceinline__ u64 wave_sum_u64(u64 x) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d, 64);
-    return x;
-}
-
-__device__ __forceinline__ int wave_min_i32(int x) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x = min(x, __shfl_xor(x, d, 64));
-    return x;
-}
 
 // deg[] as the memory holds it (agent scope: not a line of this CU's L1): core_scan / core_tail
 // read a vertex's word again after other launches or levels changed it, and must not see a peeled
@@ -64,17 +44,6 @@ __device__ __forceinline__ int wave_min_i32(int x) {
 // (see the head of this file), and the fresh read measured 2 - 3 % slower.
 __device__ __forceinline__ int32_t deg_now(const int32_t* deg, int64_t v) {
     return __hip_atomic_load(&deg[v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The calling wave's lanes with `take` set append v to list (one atomicAdd on *count per wave).
-__device__ __forceinline__ void wave_append(bool take, int32_t v, int32_t* list, u64* count) {
-    const u64 qm = __ballot(take);
-    if (!qm) return;
-    const int lead = __ffsll(static_cast<long long>(qm)) - 1;
-    u64 base = 0;
-    if (lane() == lead) base = atomicAdd(count, static_cast<u64>(__popcll(qm)));
-    base = __shfl(base, lead, 64);
-    if (take) list[base + __popcll(qm & ((1ULL << lane()) - 1))] = v;
 }
 
 // ---------------------------------------------------------------- backward lists
@@ -88,28 +57,20 @@ __global__ void __launch_bounds__(kBlock) core_bwd_count(const int32_t* __restri
 // to lanes as above: 64 consecutive rows a wave, a row of 64 entries or more by the whole wave.
 __global__ void __launch_bounds__(kBlock) core_bwd_fill(const int64_t* __restrict__ foff, const int32_t* __restrict__ fadj,
                                                         int64_t n, u64* cursor, int32_t* badj) {
-    const int64_t words = (n + 63) >> 6;
-    for (int64_t b = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock; b < words;
-         b += static_cast<int64_t>(gridDim.x) * kWavesPerBlock) {
-        const int64_t wd = b + (threadIdx.x >> 6);
-        const int64_t v = (wd << 6) + lane();
+    for_each_row_64(n, [&](int64_t v, bool live) {
         int64_t fb = 0, fl = 0;
-        if (wd < words && v < n) {
+        if (live) {
             fb = foff[v];
             fl = foff[v + 1] - fb;
         }
-        const bool wide = fl >= 64;
-        if (!wide)
+        lane_or_wave(fl >= 64, [&] {
             for (int64_t j = 0; j < fl; ++j) badj[atomicAdd(&cursor[fadj[fb + j]], 1ULL)] = static_cast<int32_t>(v);
-        u64 big = __ballot(wide);
-        while (big) {
-            const int src = __ffsll(static_cast<long long>(big)) - 1;
-            big &= big - 1;
+        }, [&](int src) {
             const int64_t sb = __shfl(fb, src, 64), sl = __shfl(fl, src, 64);
-            const int32_t sv = static_cast<int32_t>((wd << 6) + src);
+            const int32_t sv = static_cast<int32_t>(v - lane() + src);
             for (int64_t j = lane(); j < sl; j += 64) badj[atomicAdd(&cursor[fadj[sb + j]], 1ULL)] = sv;
-        }
-    }
+        });
+    });
 }
 
 __global__ void core_deg_init(const int64_t* __restrict__ d, int64_t n, int32_t* deg) {
@@ -141,20 +102,15 @@ __device__ __forceinline__ void peel_rows(bool has, int32_t v, const CoreLists& 
         fb = L.foff[v]; fl = L.foff[v + 1] - fb;
         bb = L.boff[v]; bl = L.boff[v + 1] - bb;
     }
-    const bool wide = has && fl + bl >= wave_row;
-    if (has && !wide) {
+    lane_or_wave(has && fl + bl >= wave_row, [&] {
         for (int64_t j = 0; j < fl; ++j) { const int32_t u = L.fadj[fb + j]; if (visit(deg, u, k, mn)) drop(u); }
         for (int64_t j = 0; j < bl; ++j) { const int32_t u = L.badj[bb + j]; if (visit(deg, u, k, mn)) drop(u); }
-    }
-    u64 big = __ballot(wide);
-    while (big) {
-        const int src = __ffsll(static_cast<long long>(big)) - 1;
-        big &= big - 1;
+    }, [&](int src) {
         const int64_t sfb = __shfl(fb, src, 64), sfl = __shfl(fl, src, 64);
         const int64_t sbb = __shfl(bb, src, 64), sbl = __shfl(bl, src, 64);
         for (int64_t j = lane(); j < sfl; j += 64) { const int32_t u = L.fadj[sfb + j]; if (visit(deg, u, k, mn)) drop(u); }
         for (int64_t j = lane(); j < sbl; j += 64) { const int32_t u = L.badj[sbb + j]; if (visit(deg, u, k, mn)) drop(u); }
-    }
+    });
 }
 
 // The workgroup's LDS queue: two buffers of kCoreQueue entries; count[b] may run past the
@@ -189,12 +145,6 @@ __device__ __forceinline__ unsigned drain(LdsQueue& s, unsigned cap, const CoreL
         if (threadIdx.x == 0) s.count[b] = 0;
         __syncthreads();
     }
-}
-
-// The smallest degree above k as max(INT32_MAX - degree): the counters are zeroed between rounds.
-__device__ __forceinline__ void publish_min(int mn, u64* word) {
-    mn = wave_min_i32(mn);
-    if (lane() == 0 && mn != INT_MAX) atomicMax(word, static_cast<u64>(INT_MAX - mn));
 }
 
 // Level k's scan of the alive list (list == nullptr: every vertex): a vertex whose degree reads k
@@ -247,7 +197,7 @@ __global__ void __launch_bounds__(kBlock) core_peel(const int32_t* __restrict__ 
     }
     publish_min(mn, &cnt->red[0]);
     // drops = the spills (per lane) + what the workgroup drained (the same count on every thread)
-    spilled = wave_sum_u64(spilled);
+    spilled = wave_sum(spilled);
     if (lane() == 0 && spilled) atomicAdd(&cnt->mf, spilled);
     if (threadIdx.x == 0 && drained) atomicAdd(&cnt->mf, drained);
 }
@@ -272,7 +222,7 @@ __global__ void __launch_bounds__(kBlock) core_tail(const int32_t* __restrict__ 
             const int32_t d = deg_now(deg, list ? list[i] : static_cast<int32_t>(i));
             if (d > k) mn = min(mn, d);
         }
-        mn = wave_min_i32(mn);
+        mn = wave_min(mn);
         if (lane() == 0 && mn != INT_MAX) atomicMin(&s_min, mn);
         __syncthreads();
         const int m = s_min;
@@ -311,11 +261,8 @@ __global__ void __launch_bounds__(kBlock) core_finish(const int32_t* __restrict_
         at_top += c == top;
         mx = max(mx, static_cast<u64>(c));
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        at_top += __shfl_xor(at_top, d, 64);
-        mx = max(mx, static_cast<u64>(__shfl_xor(mx, d, 64)));
-    }
+    at_top = wave_sum(at_top);
+    mx = wave_max(mx);
     if (lane() == 0) {
         if (at_top) atomicAdd(&tot[0], at_top);
         if (mx) atomicMax(&tot[1], mx);
@@ -326,27 +273,27 @@ __global__ void __launch_bounds__(kBlock) core_finish(const int32_t* __restrict_
 
 // ---------------------------------------------------------------- launchers
 hipError_t k_core_bwd_count(const int32_t* fadj, int64_t fnnz, int64_t* bcnt, hipStream_t s) {
-    core_bwd_count<<<core_grid(fnnz), kBlock, 0, s>>>(fadj, fnnz, reinterpret_cast<u64*>(bcnt));
+    core_bwd_count<<<grid_for(fnnz, 2048), kBlock, 0, s>>>(fadj, fnnz, reinterpret_cast<u64*>(bcnt));
     return hipGetLastError();
 }
 hipError_t k_core_bwd_fill(const int64_t* foff, const int32_t* fadj, int64_t n, int64_t* cursor, int32_t* badj,
                            hipStream_t s) {
-    core_bwd_fill<<<core_grid(((n + 63) / 64) * 64, 1 << 20), kBlock, 0, s>>>(foff, fadj, n, reinterpret_cast<u64*>(cursor), badj);
+    core_bwd_fill<<<grid_for(((n + 63) / 64) * 64, 1 << 20), kBlock, 0, s>>>(foff, fadj, n, reinterpret_cast<u64*>(cursor), badj);
     return hipGetLastError();
 }
 hipError_t k_core_deg_init(const int64_t* d, int64_t n, int32_t* deg, hipStream_t s) {
-    core_deg_init<<<core_grid(n), kBlock, 0, s>>>(d, n, deg);
+    core_deg_init<<<grid_for(n, 2048), kBlock, 0, s>>>(d, n, deg);
     return hipGetLastError();
 }
 hipError_t k_core_scan(const int32_t* list, int64_t len, const int32_t* deg, int32_t k, int32_t* queue, int32_t* keep,
                        Counters* cnt, hipStream_t s) {
-    core_scan<<<core_grid(len), kBlock, 0, s>>>(list, len, deg, k, queue, keep, cnt);
+    core_scan<<<grid_for(len, 2048), kBlock, 0, s>>>(list, len, deg, k, queue, keep, cnt);
     return hipGetLastError();
 }
 hipError_t k_core_peel(const int32_t* cur, int64_t qlen, const CoreView& g, int32_t* deg, int32_t k, int64_t wave_row,
                        int64_t lds_cap, int32_t* next, int64_t n, Counters* cnt, hipStream_t s) {
     const unsigned cap = static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(lds_cap, kCoreQueue)));
-    core_peel<<<core_grid(qlen), kBlock, 0, s>>>(cur, qlen, g, deg, k, wave_row, cap,
+    core_peel<<<grid_for(qlen, 2048), kBlock, 0, s>>>(cur, qlen, g, deg, k, wave_row, cap,
                                                 next, n, cnt);
     return hipGetLastError();
 }
@@ -357,7 +304,7 @@ hipError_t k_core_tail(const int32_t* list, int64_t len, const CoreView& g, int3
 }
 hipError_t k_core_finish(const int32_t* deg, int64_t n, int32_t top, int64_t* core, unsigned long long* tot,
                          hipStream_t s) {
-    core_finish<<<core_grid(n), kBlock, 0, s>>>(deg, n, top, core, tot);
+    core_finish<<<grid_for(n, 2048), kBlock, 0, s>>>(deg, n, top, core, tot);
     return hipGetLastError();
 }
 

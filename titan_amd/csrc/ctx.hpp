@@ -201,6 +201,29 @@ inline int turn_checked(tgo_ctx* ctx, const char* what) {
     return TGO_OK;
 }
 
+// The peel loops' bookkeeping (api_kcore.cpp, api_truss.cpp).  level_min: the smallest value above
+// the level that a scan or peel launch left in Counters::red[0] as max(INT32_MAX - value)
+// (wave.hpp publish_min), INT64_MAX when it published none.
+inline int64_t level_min(unsigned long long word) {
+    return word ? static_cast<int64_t>(INT32_MAX) - static_cast<int64_t>(word) : INT64_MAX;
+}
+// The alive items a level's scan reads: list[0, len), null = every item of [0, len).  A scan given
+// keep_buffer() writes the items still alive there, and adopt(their number) makes that the list.
+struct AliveList {
+    const int32_t* list;
+    int64_t len;
+    int spare;                  // the buffer the list is not in
+    int32_t* buffers[2];
+    AliveList(int64_t n, int32_t* b0, int32_t* b1) : list(nullptr), len(n), spare(0), buffers{b0, b1} {}
+    bool wants_rebuild(int64_t alive) const { return 2 * alive <= len; }       // the list has at least halved
+    int32_t* keep_buffer() const { return buffers[spare]; }
+    void adopt(int64_t new_len) {
+        list = buffers[spare];
+        spare ^= 1;
+        len = new_len;
+    }
+};
+
 // `count` device words (on the ctx stream, after the work queued so far) to out through the counter
 // page, kCounterWords words a publish: a tiny kernel and a spin instead of a copy and a stream wait.
 inline int read_words(tgo_ctx* ctx, const int64_t* dev, int64_t count, int64_t* out) {

@@ -951,10 +951,12 @@ hipError_t k_cc_count_own(const int64_t* label, const int64_t* tid, int64_t n, u
 
 // Triangle counting (tri.hip).  Forward lists: k_tri_fwd_count writes |fwd(v)| to fcnt (n + 1,
 // fcnt[n] = 0), d(v) to deg and raises *max_fwd to the longest forward row; k_tri_fwd_fill writes
-// the rows at their scanned offsets.  k_tri_count adds every triangle to tri (n, zero before) at its
-// three corners: rows of >= wave_row forward entries by their wave, rows of >= block_row entries
-// (at most kTriLdsEntries) by a workgroup from LDS, through the queues wlist / blist (n each) and
-// q (4 words, zero before: block rows, wave rows and the two kernels' tickets).
+// the rows at their scanned offsets.
+// The walk (tri_walk.hpp; k_tri_count and k_truss_support are its two users): every triangle of the
+// forward lists is found once and credited — rows of >= wave_row forward entries by their wave,
+// rows of >= block_row entries (at most kTriLdsEntries; max_fwd = the longest row) by a workgroup
+// from LDS, through the queues wlist / blist (n each) and q (4 words, zero before: block rows, wave
+// rows and the two kernels' tickets).  k_tri_count credits the three corners in tri (n, zero before).
 // k_tri_finish: lcc, and tot[0..3] += sum tri, wedges, sum d, max tri.
 constexpr int64_t kTriLdsEntries = 16384;    // entries + their counters: 128 KB of the CU's 160 KB LDS
 hipError_t k_tri_fwd_count(const DevCsr& out, const DevCsr& in, int64_t n, int64_t* fcnt, int64_t* deg,
@@ -998,8 +1000,8 @@ hipError_t k_core_finish(const int32_t* deg, int64_t n, int32_t top, int64_t* co
 
 // k-truss decomposition (truss.hip).  Lists: k_truss_edge_rows writes erow (the row of every forward
 // entry), k_truss_seid the edge id of every entry of the simple adjacency (*err raised when the two
-// lists disagree).  k_truss_support adds every triangle to the support of its three edges (sup: one
-// int32 per forward entry, zero before; row classes and queues as k_tri_count).  k_truss_scan (level l
+// lists disagree).  k_truss_support: the walk (above, at k_tri_count) with every triangle credited to
+// its three edges (sup: one int32 per forward entry, zero before).  k_truss_scan (level l
 // over the alive list; list null = every edge; queue null = none): the cnt->qlen alive edges with
 // sup <= l to queue (marked -1 in tr), with keep the cnt->mf others to keep, cnt->red[0] = INT32_MAX -
 // the smallest sup > l (0: none).  k_truss_peel (one sub-round of level l): the edges that drop to the

@@ -1,22 +1,21 @@
 // frontier.hpp — device building blocks shared by the frontier kernels (bfs.hip, delta.hip,
 // msbfs.hip): edge-balanced load-balanced search over a vertex queue, block-aggregated
-// queue appends, and two-pass bitmap extraction.  Include from exactly those .hip files
-// (everything here is in an anonymous namespace, one copy per translation unit).
+// queue appends, and two-pass bitmap extraction.  Any .hip file that walks a frontier includes it;
+// kBlock, kWavesPerBlock, lane() and the wave-level helpers come from wave.hpp, which the
+// programs without a frontier include alone (everything in both is in an anonymous namespace,
+// one copy per translation unit).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include "engine.hpp"
+#include "wave.hpp"
 
 namespace tgo {
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / 64;
 constexpr int kEdgesPerThread = 8;
 constexpr int kTileEdges = kBlock * kEdgesPerThread;   // 2048 queue entries' edges per block tile
 constexpr int kLdsEntries = kTileEdges + 2;
-
-__device__ __forceinline__ int lane() { return static_cast<int>(threadIdx.x & 63); }
 
 // Entries of u over the one or two lists of a view.
 __device__ __forceinline__ int64_t push_degree(const View& v, int64_t u) {

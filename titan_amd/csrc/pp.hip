@@ -38,20 +38,14 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
-#include "frontier.hpp"
+#include "engine.hpp"
+#include "wave.hpp"
 
 namespace tgo {
 namespace {
 
-using u64 = unsigned long long;
-
 constexpr u64 kPpOne = 1ULL << 32;              // a whole vote
 constexpr u64 kPpSMask = (1ULL << 33) - 1;      // S of a vote word (S <= 2^32)
-
-inline int pp_grid(int64_t work, int64_t cap = 1 << 16) {
-    const int64_t g = (work + kBlock - 1) / kBlock;
-    return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(g, cap)));
-}
 
 __device__ __forceinline__ void wave_sync() {          // a wave's LDS writes visible to its own later reads
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -114,17 +108,6 @@ __device__ __forceinline__ int64_t row_len(const View& r, int64_t v) {
     return l;
 }
 
-// First index of a[0, l) that is >= u (a sorted).
-__device__ __forceinline__ int64_t lower_bound(const int32_t* __restrict__ a, int64_t l, int32_t u) {
-    int64_t lo = 0, hi = l;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a[mid] < u) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // ---------------------------------------------------------------- group folds (G = 1, 64, 256)
 struct PpShared {
     u64 t[kWavesPerBlock];
@@ -164,11 +147,8 @@ __device__ __forceinline__ void group_sync() {
 template <int G>
 __device__ __forceinline__ void group_span(bool& any, int32_t& lo, int32_t& hi, PpShared& sh) {
     any = __ballot(any) != 0;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        lo = min(lo, __shfl_xor(lo, d, 64));
-        hi = max(hi, __shfl_xor(hi, d, 64));
-    }
+    lo = wave_min(lo);
+    hi = wave_max(hi);
     if (G != 256) return;
     const int w = threadIdx.x >> 6;
     __syncthreads();
@@ -182,20 +162,9 @@ __device__ __forceinline__ void group_span(bool& any, int32_t& lo, int32_t& hi, 
     }
 }
 
-// The calling wave's lanes with `take` set append v to list (one atomicAdd on *count per wave).  A
-// vertex is appended to one queue once, so a queue (n + 1 entries) cannot overflow.
-__device__ __forceinline__ void wave_append(bool take, int32_t v, int32_t* list, u64* count) {
-    const u64 qm = __ballot(take);
-    if (!qm) return;
-    const int lead = __ffsll(static_cast<long long>(qm)) - 1;
-    u64 base = 0;
-    if (lane() == lead) base = atomicAdd(count, static_cast<u64>(__popcll(qm)));
-    base = __shfl(base, lead, 64);
-    if (take) list[base + __popcll(qm & ((1ULL << lane()) - 1))] = v;
-}
-
 // ---------------------------------------------------------------- init
-// The first votes (label = rank, S by d(v) = the entries of v's send rows) and the two row queues.
+// The first votes (label = rank, S by d(v) = the entries of v's send rows) and the two row queues
+// (wave_append: a vertex is appended to one queue once, so a queue of n + 1 entries cannot overflow).
 template <bool DIST>
 __global__ void __launch_bounds__(kBlock) pp_init(View recv, View send, int64_t n, const int32_t* __restrict__ rank,
                                                   void* cur, int64_t wave_row, int64_t block_row, int32_t* wq, u64* wcount,
@@ -250,8 +219,7 @@ __device__ __forceinline__ int32_t group_row(int64_t it, const View& recv, int64
 template <int G>
 __device__ __forceinline__ void count_changed(u64 moved, u64* changed) {
     if (G == 1) {
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) moved += __shfl_xor(moved, d, 64);
+        moved = wave_sum(moved);
         if (lane() == 0 && moved) atomicAdd(changed, moved);
     } else if (moved) {
         atomicAdd(changed, moved);
@@ -498,11 +466,8 @@ __global__ void __launch_bounds__(kBlock) pp_census(const int32_t* __restrict__ 
         mine += h != 0;
         most = max(most, h);
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        mine += __shfl_xor(mine, d, 64);
-        most = max(most, __shfl_xor(most, d, 64));
-    }
+    mine = wave_sum(mine);
+    most = wave_max(most);
     if (lane() == 0 && mine) {
         atomicAdd(clusters, mine);
         atomicMax(largest, most);
@@ -521,8 +486,8 @@ hipError_t pp_round(const PpRun& r, bool first, int tier, const void* cur, void*
     const size_t lds = static_cast<size_t>(r.slots) * kWavesPerBlock * (sizeof(u64) + sizeof(int32_t));
     if (tier == 0) {
         const int64_t lane_row = std::min(r.wave_row, r.block_row);     // shorter rows are in neither queue
-        if (first) pp_first<DIST, 1><<<pp_grid(r.n), kBlock, 0, s>>>(r.recv, r.n, cur, next, lane_row, nullptr, 0, changed);
-        else pp_vote_lane<DIST><<<pp_grid(r.n), kBlock, 0, s>>>(r.recv, r.n, cur, next, lane_row, changed);
+        if (first) pp_first<DIST, 1><<<grid_for(r.n, 1 << 16), kBlock, 0, s>>>(r.recv, r.n, cur, next, lane_row, nullptr, 0, changed);
+        else pp_vote_lane<DIST><<<grid_for(r.n, 1 << 16), kBlock, 0, s>>>(r.recv, r.n, cur, next, lane_row, changed);
     } else if (tier == 1 && r.nwave > 0) {
         if (first) pp_first<DIST, 64><<<pp_wave_grid(r.nwave), kBlock, 0, s>>>(r.recv, r.n, cur, next, 0, r.wq, r.nwave, changed);
         else pp_vote_table<DIST, 64><<<pp_wave_grid(r.nwave), kBlock, lds, s>>>(r.recv, cur, next, r.slots, r.wq, r.nwave, changed);
@@ -537,10 +502,10 @@ hipError_t pp_round(const PpRun& r, bool first, int tier, const void* cur, void*
 
 hipError_t k_pp_init(const PpRun& r, const View& send, const int32_t* rank, void* cur, Counters* cnt, hipStream_t s) {
     if (r.distribute)
-        pp_init<true><<<pp_grid(r.n, 2048), kBlock, 0, s>>>(r.recv, send, r.n, rank, cur, r.wave_row, r.block_row, r.wq,
+        pp_init<true><<<grid_for(r.n, 2048), kBlock, 0, s>>>(r.recv, send, r.n, rank, cur, r.wave_row, r.block_row, r.wq,
                                                              &cnt->qlen, r.bq, &cnt->mf);
     else
-        pp_init<false><<<pp_grid(r.n, 2048), kBlock, 0, s>>>(r.recv, send, r.n, rank, cur, r.wave_row, r.block_row, r.wq,
+        pp_init<false><<<grid_for(r.n, 2048), kBlock, 0, s>>>(r.recv, send, r.n, rank, cur, r.wave_row, r.block_row, r.wq,
                                                               &cnt->qlen, r.bq, &cnt->mf);
     return hipGetLastError();
 }
@@ -552,9 +517,9 @@ hipError_t k_pp_round(const PpRun& r, bool first, int tier, const void* cur, voi
 
 hipError_t k_pp_finish(const PpRun& r, const void* cur, const int32_t* inv, const int64_t* tid, int64_t* label, int32_t* hist,
                        Counters* cnt, hipStream_t s) {
-    if (r.distribute) pp_finish<true><<<pp_grid(r.n, 2048), kBlock, 0, s>>>(cur, r.n, inv, tid, label, hist);
-    else pp_finish<false><<<pp_grid(r.n, 2048), kBlock, 0, s>>>(cur, r.n, inv, tid, label, hist);
-    pp_census<<<pp_grid(r.n, 2048), kBlock, 0, s>>>(hist, r.n, &cnt->qlen, &cnt->red[0]);
+    if (r.distribute) pp_finish<true><<<grid_for(r.n, 2048), kBlock, 0, s>>>(cur, r.n, inv, tid, label, hist);
+    else pp_finish<false><<<grid_for(r.n, 2048), kBlock, 0, s>>>(cur, r.n, inv, tid, label, hist);
+    pp_census<<<grid_for(r.n, 2048), kBlock, 0, s>>>(hist, r.n, &cnt->qlen, &cnt->red[0]);
     return hipGetLastError();
 }
 

@@ -34,55 +34,16 @@
 // caches, so that launch read every word as the memory held it.  Wave = 64 lanes.  Rows go to
 // lanes by length: one lane per row, the whole wave from wave_row entries on.
 #include <hip/hip_runtime.h>
-#include <algorithm>
-#include <climits>
-#include "frontier.hpp"
+#include "engine.hpp"
+#include "wave.hpp"
 
 namespace tgo {
 namespace {
 
-using u64 = unsigned long long;
-
 enum : int { kTrim = 0, kForward = 1, kBackward = 2, kColourBack = 3 };
-
-inline int scc_grid(int64_t work, int64_t cap = 2048) {
-    const int64_t g = (work + kBlock - 1) / kBlock;
-    return static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(g, cap)));
-}
-
-__device__ __forceinline__ u64 wave_sum(u64 x) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d, 64);
-    return x;
-}
-
-__device__ __forceinline__ long long wave_min_ll(long long x) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const long long y = __shfl_xor(x, d, 64);
-        x = y < x ? y : x;
-    }
-    return x;
-}
 
 __device__ __forceinline__ int32_t now(const int32_t* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The calling wave's lanes with `take` set append v to list (one atomicAdd on *count per wave);
-// an entry past cap is dropped and raises *err (every list here holds n entries: a broken invariant).
-__device__ __forceinline__ void wave_append(bool take, int32_t v, int32_t* list, u64* count, u64 cap, u64* err) {
-    const u64 qm = __ballot(take);
-    if (!qm) return;
-    const int lead = __ffsll(static_cast<long long>(qm)) - 1;
-    u64 base = 0;
-    if (lane() == lead) base = atomicAdd(count, static_cast<u64>(__popcll(qm)));
-    base = __shfl(base, lead, 64);
-    if (take) {
-        const u64 slot = base + __popcll(qm & ((1ULL << lane()) - 1));
-        if (slot < cap) list[slot] = v;
-        else atomicMax(err, 1ULL);
-    }
 }
 
 // The calling wave walks one list's row of its lanes' vertices (has: the lane holds one); every lane
@@ -95,17 +56,13 @@ __device__ __forceinline__ void rows(bool has, int32_t v, int32_t tag, const int
         b = off[v];
         l = off[v + 1] - b;
     }
-    const bool wide = has && l >= wave_row;
-    if (has && !wide)
+    lane_or_wave(has && l >= wave_row, [&] {
         for (int64_t j = 0; j < l; ++j) f(v, tag, adj[b + j]);
-    u64 big = __ballot(wide);
-    while (big) {
-        const int src = __ffsll(static_cast<long long>(big)) - 1;
-        big &= big - 1;
+    }, [&](int src) {
         const int64_t sb = __shfl(b, src, 64), sl = __shfl(l, src, 64);
         const int32_t sv = __shfl(v, src, 64), st = __shfl(tag, src, 64);
         for (int64_t j = lane(); j < sl; j += 64) f(sv, st, adj[sb + j]);
-    }
+    });
 }
 
 // The entries of the lane's own row that do not name v itself (wide rows counted by the wave).
@@ -116,21 +73,17 @@ __device__ __forceinline__ int32_t row_degree(bool has, int32_t v, const int64_t
         b = off[v];
         l = off[v + 1] - b;
     }
-    const bool wide = has && l >= wave_row;
     u64 mine = 0;
-    if (has && !wide)
+    lane_or_wave(has && l >= wave_row, [&] {
         for (int64_t j = 0; j < l; ++j) mine += adj[b + j] != v;
-    u64 big = __ballot(wide);
-    while (big) {
-        const int src = __ffsll(static_cast<long long>(big)) - 1;
-        big &= big - 1;
+    }, [&](int src) {
         const int64_t sb = __shfl(b, src, 64), sl = __shfl(l, src, 64);
         const int32_t sv = __shfl(v, src, 64);
         u64 part = 0;
         for (int64_t j = lane(); j < sl; j += 64) part += adj[sb + j] != sv;
         part = wave_sum(part);
         if (lane() == src) mine = part;
-    }
+    });
     return static_cast<int32_t>(mine);
 }
 
@@ -272,8 +225,7 @@ __global__ void __launch_bounds__(kBlock) scc_pivot_pick(SccState S, int64_t n, 
         if (step == 0) best = max(best, p);
         else if (p == product) best = max(best, 0xFFFFFFFFULL - static_cast<u64>(v));
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) best = max(best, static_cast<u64>(__shfl_xor(best, d, 64)));
+    best = wave_max(best);
     if (lane() == 0 && best) atomicMax(&cnt->red[0], best);
 }
 
@@ -517,7 +469,7 @@ __global__ void __launch_bounds__(kBlock) scc_fold(const int32_t* __restrict__ c
             const int lead = __ffsll(static_cast<long long>(m)) - 1;
             const int32_t r0 = __shfl(r, lead, 64);
             const bool mine = todo && r == r0;
-            const long long lo = wave_min_ll(mine ? id : INT64_MAX);
+            const long long lo = wave_min(mine ? id : INT64_MAX);
             const int cnt = __popcll(__ballot(mine));
             if (lane() == lead) {
                 atomicMin(&minid[r0], lo);
@@ -553,8 +505,7 @@ __global__ void __launch_bounds__(kBlock) scc_label(const int32_t* __restrict__ 
     comps = wave_sum(comps);
     single = wave_sum(single);
     retired = wave_sum(retired);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) largest = max(largest, static_cast<u64>(__shfl_xor(largest, d, 64)));
+    largest = wave_max(largest);
     if (lane() == 0) {
         if (comps) atomicAdd(&cnt->qlen, comps);
         if (single) atomicAdd(&cnt->mf, single);
@@ -568,13 +519,13 @@ __global__ void __launch_bounds__(kBlock) scc_label(const int32_t* __restrict__ 
 // ---------------------------------------------------------------- launchers
 hipError_t k_scc_init(const SccGraph& g, int64_t n, const SccState& st, bool trim, int64_t wave_row, int32_t* queue,
                       Counters* cnt, hipStream_t s) {
-    scc_init<<<scc_grid(((n + 63) / 64) * 64, 1 << 20), kBlock, 0, s>>>(g, n, st, trim ? 1 : 0, wave_row, queue, cnt);
+    scc_init<<<grid_for(((n + 63) / 64) * 64, 1 << 20), kBlock, 0, s>>>(g, n, st, trim ? 1 : 0, wave_row, queue, cnt);
     return hipGetLastError();
 }
 hipError_t k_scc_walk(int mode, const int32_t* cur, int64_t qlen, const SccGraph& g, const SccState& st, int64_t wave_row,
                       int32_t* next, int64_t n, Counters* cnt, hipStream_t s) {
     const unsigned cap = kSccQueue;
-    const int grid = scc_grid(qlen);
+    const int grid = grid_for(qlen, 2048);
     switch (mode) {
     case kTrim: scc_walk<kTrim><<<grid, kBlock, 0, s>>>(cur, qlen, g, st, wave_row, cap, next, n, cnt); break;
     case kForward: scc_walk<kForward><<<grid, kBlock, 0, s>>>(cur, qlen, g, st, wave_row, cap, next, n, cnt); break;
@@ -586,7 +537,7 @@ hipError_t k_scc_walk(int mode, const int32_t* cur, int64_t qlen, const SccGraph
 }
 hipError_t k_scc_pivot_pick(const SccState& st, int64_t n, int step, unsigned long long product, Counters* cnt,
                             hipStream_t s) {
-    scc_pivot_pick<<<scc_grid(n), kBlock, 0, s>>>(st, n, step, product, cnt);
+    scc_pivot_pick<<<grid_for(n, 2048), kBlock, 0, s>>>(st, n, step, product, cnt);
     return hipGetLastError();
 }
 hipError_t k_scc_seed(const SccState& st, int32_t pivot, int32_t bits, int32_t* queue, hipStream_t s) {
@@ -595,26 +546,26 @@ hipError_t k_scc_seed(const SccState& st, int32_t pivot, int32_t bits, int32_t* 
 }
 hipError_t k_scc_retire(const int32_t* list, int64_t len, const SccState& st, int32_t bits, int32_t rep, int32_t* queue,
                         int64_t n, Counters* cnt, hipStream_t s) {
-    scc_retire<<<scc_grid(((len + 63) / 64) * 64), kBlock, 0, s>>>(list, len, st, bits, rep, queue, n, cnt);
+    scc_retire<<<grid_for(((len + 63) / 64) * 64, 2048), kBlock, 0, s>>>(list, len, st, bits, rep, queue, n, cnt);
     return hipGetLastError();
 }
 hipError_t k_scc_live_list(const int32_t* list, int64_t len, const SccState& st, int32_t* keep, int32_t* pos, int64_t n,
                            Counters* cnt, hipStream_t s) {
-    scc_live_list<<<scc_grid(((len + 63) / 64) * 64), kBlock, 0, s>>>(list, len, st, keep, pos, n, cnt);
+    scc_live_list<<<grid_for(((len + 63) / 64) * 64, 2048), kBlock, 0, s>>>(list, len, st, keep, pos, n, cnt);
     return hipGetLastError();
 }
 hipError_t k_scc_colour_init(const int32_t* list, int64_t len, const SccState& st, hipStream_t s) {
-    scc_colour_init<<<scc_grid(len), kBlock, 0, s>>>(list, len, st);
+    scc_colour_init<<<grid_for(len, 2048), kBlock, 0, s>>>(list, len, st);
     return hipGetLastError();
 }
 hipError_t k_scc_colour_round(const int32_t* list, int64_t len, const SccGraph& g, const SccState& st, int64_t wave_row,
                               Counters* cnt, hipStream_t s) {
-    scc_colour_round<<<scc_grid(((len + 63) / 64) * 64), kBlock, 0, s>>>(list, len, g, st, wave_row, cnt);
+    scc_colour_round<<<grid_for(((len + 63) / 64) * 64, 2048), kBlock, 0, s>>>(list, len, g, st, wave_row, cnt);
     return hipGetLastError();
 }
 hipError_t k_scc_roots(const int32_t* list, int64_t len, const SccState& st, int32_t* queue, int64_t n, Counters* cnt,
                        hipStream_t s) {
-    scc_roots<<<scc_grid(((len + 63) / 64) * 64), kBlock, 0, s>>>(list, len, st, queue, n, cnt);
+    scc_roots<<<grid_for(((len + 63) / 64) * 64, 2048), kBlock, 0, s>>>(list, len, st, queue, n, cnt);
     return hipGetLastError();
 }
 hipError_t k_scc_tail(const int32_t* list, int64_t len, const SccGraph& g, int32_t* comp, const int32_t* pos, bool trim,
@@ -624,12 +575,12 @@ hipError_t k_scc_tail(const int32_t* list, int64_t len, const SccGraph& g, int32
     return hipGetLastError();
 }
 hipError_t k_scc_fold(const int32_t* comp, const int64_t* tid, int64_t n, int64_t* minid, int32_t* size, hipStream_t s) {
-    scc_fold<<<scc_grid(((n + 63) / 64) * 64), kBlock, 0, s>>>(comp, tid, n, reinterpret_cast<long long*>(minid), size);
+    scc_fold<<<grid_for(((n + 63) / 64) * 64, 2048), kBlock, 0, s>>>(comp, tid, n, reinterpret_cast<long long*>(minid), size);
     return hipGetLastError();
 }
 hipError_t k_scc_label(const int32_t* comp, const int64_t* minid, const int32_t* size, int64_t n, int64_t* label,
                        Counters* cnt, hipStream_t s) {
-    scc_label<<<scc_grid(n), kBlock, 0, s>>>(comp, reinterpret_cast<const long long*>(minid), size, n, label, cnt);
+    scc_label<<<grid_for(n, 2048), kBlock, 0, s>>>(comp, reinterpret_cast<const long long*>(minid), size, n, label, cnt);
     return hipGetLastError();
 }
 
