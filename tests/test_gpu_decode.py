@@ -1,13 +1,15 @@
 """GPU: the device row decoder (decode.hip) against the host decoder on the
 same rows — the staging both produce is loaded and must give the same graph: ids, counters
-(ghosts, truncated lists, skipped rows, vertex cuts) and traversal results; malformed rows
-fail the same way.  TGO_HOST_DECODE=1 selects the host decoder (read on every call)."""
+(ghosts, truncated lists, skipped rows, vertex cuts), the assembled lists entry for entry
+(tests/loaded_lists.py) and traversal results; malformed rows fail the same way.
+TGO_HOST_DECODE=1 selects the host decoder (read on every call)."""
 import random
 
 import numpy as np
 import pytest
 
 import fulgora as fr
+import loaded_lists as ll
 from conftest import load_fixture
 from titan_amd import Engine, Schema, TitanException, rmat_edges
 from titan_amd import _lib as L
@@ -31,6 +33,11 @@ def assert_same(h, d, seeds, scope, n, weighted=False):
     for k in STAT_KEYS:
         assert h.stats()[k] == d.stats()[k], k
     assert np.array_equal(h.vertex_ids(), d.vertex_ids())
+    he, de = ll.engine_entries(h, weights=weighted), ll.engine_entries(d, weights=weighted)
+    assert sorted(he) == sorted(de)
+    for k in he:                                   # every assembled entry: row, direction, neighbour, weight
+        assert np.array_equal(he[k], de[k]), k
+        assert len(he[k]) == d.stats()[ll.COUNTERS[k]]
     for s in seeds:
         assert np.array_equal(h.bfs(int(s), n, scope), d.bfs(int(s), n, scope))
         if weighted:

@@ -102,8 +102,10 @@ __global__ void __launch_bounds__(kBlock) dec_entries(const int64_t* __restrict_
         sel[p] = 1;
         other[p] = is_partitioned_vertex(de.other, pb) ? canonical_vertex_id(de.other, pb) : de.other;  // :89
         dir[p] = static_cast<uint8_t>(de.dir);
-        w[p] = weighted ? (de.has_weight ? de.weight : kMissingWeight) : 1;
-        if (wv) wv[p] = de.has_weight ? de.weight64 : 0;          // wide keys (Long / Double)
+        // wide keys (Long / Double): presence comes from has_weight alone (the value's low 32
+        // bits may equal kMissingWeight); compact_entries replaces the 0 by the staged position
+        w[p] = weighted ? (de.has_weight ? (wv ? 0 : de.weight) : kMissingWeight) : 1;
+        if (wv) wv[p] = de.has_weight ? de.weight64 : 0;
     }
 }
 

@@ -248,7 +248,9 @@ int decode_rows(RowStaging& st, const tgo_rows* rows, const tgo_schema* schema,
                 // messages are looked up by canonical id (VertexMemoryHandler.java:89)
                 L.other.push_back(is_partitioned_vertex(de.other, pb) ? canonical_vertex_id(de.other, pb) : de.other);
                 L.dir.push_back(static_cast<uint8_t>(de.dir));
-                L.w.push_back(opts->weight_key == 0 ? 1 : (de.has_weight ? de.weight : kMissingWeight));
+                // a wide key's column becomes the staged position below: presence comes from
+                // has_weight alone (the value's low 32 bits may equal kMissingWeight)
+                L.w.push_back(opts->weight_key == 0 ? 1 : (de.has_weight ? (wide ? 0 : de.weight) : kMissingWeight));
                 if (wide) L.wv.push_back(de.has_weight ? de.weight64 : 0);
                 ++kept;
             }
