@@ -415,6 +415,8 @@ int  tgo_trace_range_push(const char* name);
 int  tgo_trace_range_pop(void);
 /* After tgo_bfs_multi with TGO_FLAG_STATS: per seed, reached vertices and their entries. */
 int  tgo_multi_stats(tgo_ctx* ctx, int64_t* reached, int64_t* reached_entries);
+/* The distances tgo_bfs / tgo_sssp left on the device, or tgo_pagerank's ranks (the bits of the
+ * doubles).  After any other program, or a failed one: TGO_E_STATE. */
 int  tgo_copy_distances(tgo_ctx* ctx, int64_t* dist_out);
 int  tgo_pagerank(tgo_ctx* ctx, const tgo_pr_args* args, double* pr_out);
 /* OLAPTest.DegreeCounter(k) (OLAPTest.java:334-416): k-walk counts, Java int wrap. */

@@ -534,10 +534,14 @@ int tgo_sssp(tgo_ctx* ctx, const tgo_sssp_args* a, int64_t* dist_out) {
     return finish_distance_program(ctx, a->scope, a->flags, dist_out);
 }
 
-// (no last_result_check: PageRank's ranks are fetched through this too, from the same scratch)
+// PageRank's ranks are fetched through this too, from the same scratch (the bits of the doubles).  Every
+// other program that publishes through sc.dist (labels, counts, truss numbers) has a tgo_copy_* of its own.
 int tgo_copy_distances(tgo_ctx* ctx, int64_t* dist_out) {
     if (!ctx || !dist_out) return TGO_E_INVALID;
     if (!ctx->loaded) return fail(ctx, TGO_E_STATE, "no graph loaded");
+    if (ctx->res_kind != TGO_RESULT_DISTANCE && ctx->res_kind != TGO_RESULT_PAGERANK)
+        return fail(ctx, TGO_E_STATE, "tgo_bfs / tgo_sssp / tgo_pagerank is not the last program run on this ctx");
+    (void)hipSetDevice(ctx->opts.device);
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return rows_out(ctx, ctx->sc.dist, dist_out);
 }
